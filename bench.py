@@ -15,11 +15,21 @@ memory (shared by the node's ranks), cut by packet index into shards [g*N/G, (g+
 gpd_pcap_locate; each rank decodes its shard device-resident (the metric) and streamed from
 host memory in 2^24-record calls of gpd_decode_pcap_at (PCIe-inclusive, reported beside it).
 
-Rank 0 prints one JSON line with `value` in Mpackets/s (whole job), a `roofline` object for
-the decode kernel (algorithmic HBM bytes per launch — packet bytes and descriptors read,
-result records written — over the mean launch time measured with HIP events on the launch
-stream) and a `cpu_baseline` object (the C restatement of gopacket's DLP in oracle/ on
-BASELINE.md's config-1 workload, one thread and all of this host's cores).
+Rank 0 prints one JSON line with `value` in Mpackets/s (whole job), `ms_per_step` (the wall
+clock of the K timed steps / K) and a `roofline` object for the decode kernel (algorithmic HBM
+bytes per launch — packet bytes and descriptors read, result records written — over the mean
+launch time measured with HIP events on the launch stream around the same K steps).
+
+A plain run does only that: set up, settle and warm up, time the K steps, print the line.
+`--full` adds every figure that takes runs of its own: the 36-B record and other-result-form
+launches, the fast/generic split, the PCIe-inclusive rate of the same batch, the attainable-
+bandwidth probe, the other configurations (tcp64, imix, vxlan, pcap64), config 5's streamed
+leg (`--config replay`) and a `cpu_baseline` object (the C restatement of gopacket's DLP in
+oracle/ on BASELINE.md's config-1 workload, one thread and all of this host's cores).
+
+`--dump-outputs DIR` writes what the last timed step left in the result arrays (the five
+result words per packet a caller of gpd_decode receives) to DIR/<name>.npy as float64; see
+dump_outputs().
 """
 from __future__ import annotations
 
@@ -838,9 +848,50 @@ def records_form(args) -> bool:
     return args.config not in ("imix", "mixed")
 
 
+DUMP_SAMPLE = 1 << 19  # packets --dump-outputs writes: 72 B each as float64, 36 MiB in all
+DUMP_SEED = 0x5EED0D0
+
+
+def dump_rows(n: int) -> np.ndarray:
+    """The packets --dump-outputs writes: all n up to DUMP_SAMPLE, else a fixed seeded sample of
+    DUMP_SAMPLE of them (ascending), the same for every run with the same n."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path: str, res, n: int, device) -> dict:
+    """Write the result words of dump_rows(n), as they sit in `res` (a DeviceResult or _Res:
+    gpd_records or the five SoA arrays, gathered on the device) to path/<name>.npy as float64:
+    index (the packet numbers), status and csum (u32) as (k,), layers, net_hash and tp_hash
+    (u64) as (k, 2) = low and high 32-bit word, so every value is exact."""
+    import torch
+    from gopacket_amd.results import RECORD_DTYPE
+    rows = dump_rows(n)
+    idx = torch.from_numpy(rows).to(device)
+    dt = {"status": np.uint32, "csum": np.uint32, "layers": np.uint64, "net_hash": np.uint64,
+          "tp_hash": np.uint64}
+    if res.records is not None:
+        r = res.records.view(n, RECORD_DTYPE.itemsize).index_select(0, idx).cpu().numpy()
+        r = r.view(RECORD_DTYPE).reshape(-1)
+        cols = {f: r[f] for f in dt}
+    else:
+        cols = {f: getattr(res, f).index_select(0, idx).cpu().numpy().view(d) for f, d in dt.items()}
+    os.makedirs(path, exist_ok=True)
+    out = {"index": rows.astype(np.float64)}
+    for f, a in cols.items():
+        a = a.astype(dt[f])
+        if a.dtype == np.uint64:
+            a = np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=1)
+        out[f] = a.astype(np.float64)
+    for f, a in out.items():
+        np.save(os.path.join(path, f + ".npy"), a)
+    return {"dir": path, "packets": int(len(rows)), "of": n, "bytes": int(sum(a.nbytes for a in out.values()))}
+
+
 def bench_replay(args, world, rank, local, dist):
     """BASELINE config 5 on this rank: locate the shard, decode it device-resident (timed steps),
-    then stream it from host memory through gpd_decode_pcap_at (PCIe-inclusive)."""
+    then (--full) stream it from host memory through gpd_decode_pcap_at (PCIe-inclusive)."""
     import ctypes as C
 
     import torch
@@ -848,7 +899,6 @@ def bench_replay(args, world, rank, local, dist):
     from gopacket_amd import parser as P
     from gopacket_amd import pcap as NP
     from gopacket_amd._lib import GpdBatch, check, lib
-    from gopacket_amd.results import BatchResult
     n = args.packets or 10 ** 9
     threads = rank_threads(args)
     dev = torch.device("cuda", local)
@@ -945,8 +995,37 @@ def bench_replay(args, world, rank, local, dist):
     kern_ms = float(np.mean([x.elapsed_time(y) for x, y in ev]))
     st = (res.records.view(torch.int32)[0::8] if aos else res.status).cpu().numpy().view(np.uint32)
     n_err = int(np.count_nonzero((st & 3) != 0))
-    # PCIe-inclusive leg: the shard streamed from host memory in 2^24-record calls
+    dumped = dump_outputs(args.dump_outputs, res, m, dev) if args.dump_outputs and rank == 0 else None
+    t_pcie, same, pcie_diag = 0.0, True, None
     call = args.pcie_call_records or REPLAY_CHUNK  # records per gpd_decode_pcap_at call
+    if args.full:  # PCIe-inclusive leg: the shard streamed from host memory in 2^24-record calls
+        t_pcie, same, pcie_diag = replay_streamed(args, parser, rc, info, res, m, call, threads, local, dist)
+    if registered:
+        lib.gpd_host_unregister(h, cap[reg_lo:].ctypes.data)
+    # per-rank figures to rank 0
+    mine = [elapsed, kern_ms, t_pcie, float(read_bytes), float(m), float(n_err), float(same),
+            t_gen, t_locate, t_reg, t_h2d, t_index, float(registered)]
+    rows = [mine]
+    if dist:
+        t = torch.tensor(mine, dtype=torch.float64, device=COMM_DEVICE or dev)
+        g = [torch.zeros_like(t) for _ in range(world)]
+        dist.all_gather(g, t)
+        rows = [list(x.cpu().numpy()) for x in g]
+    del d_bytes, d_off, d_len, res, launches
+    if rank != 0:
+        return None
+    return replay_line(args, n, world, rows, rc, dl, len(chunks), threads, aos, settled, call, pcie_diag,
+                       dumped)
+
+
+def replay_streamed(args, parser, rc, info, res, m, call, threads, local, dist):
+    """Config 5's PCIe-inclusive leg (--full): this rank's shard streamed from host memory through
+    gpd_decode_pcap_at, `call` records per call.  Returns (seconds, whether the last call's
+    results equal the resident ones for the same records, rank-0 diagnostics)."""
+    from gopacket_amd._lib import check, lib
+    from gopacket_amd.results import BatchResult
+    cap, start, end = rc.cap, rc.start, rc.end
+    h = parser.ctx().h
     z = lambda dt: np.zeros(call, dt)
     out = BatchResult(z(np.uint32), z(np.uint64), z(np.uint64), z(np.uint64), z(np.uint32), None,
                       z(np.uint32))
@@ -1011,20 +1090,12 @@ def bench_replay(args, world, rank, local, dist):
                for f in ("status", "layers", "net_hash", "tp_hash", "csum"))
     for a in outs:
         lib.gpd_host_unregister(h, a.ctypes.data)
-    if registered:
-        lib.gpd_host_unregister(h, cap[reg_lo:].ctypes.data)
-    # per-rank figures to rank 0
-    mine = [elapsed, kern_ms, t_pcie, float(read_bytes), float(m), float(n_err), float(same),
-            t_gen, t_locate, t_reg, t_h2d, t_index, float(registered)]
-    rows = [mine]
-    if dist:
-        t = torch.tensor(mine, dtype=torch.float64, device=COMM_DEVICE or dev)
-        g = [torch.zeros_like(t) for _ in range(world)]
-        dist.all_gather(g, t)
-        rows = [list(x.cpu().numpy()) for x in g]
-    del d_bytes, d_off, d_len, res, launches
-    if rank != 0:
-        return None
+    return t_pcie, same, pcie_diag
+
+
+def replay_line(args, n, world, rows, rc, dl, nchunks, threads, aos, settled, call, pcie_diag, dumped):
+    """Config 5's JSON object from every rank's figures (rank 0); the PCIe-inclusive objects only
+    where that leg ran (--full)."""
     el_max = max(r[0] for r in rows)
     kmax = max(r[1] for r in rows)
     pcie_max = max(r[2] for r in rows)
@@ -1058,25 +1129,31 @@ def bench_replay(args, world, rank, local, dist):
                    "decode_errors": int(sum(r[5] for r in rows))},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                     "kernel_ms": round(rows[0][1] / len(chunks), 4),
-                     "kernel_ms_max_rank": round(kmax / len(chunks), 4),
-                     "launches_per_step": len(chunks),
-                     "algorithmic_bytes_per_launch": int(alg0 / len(chunks)),
+                     "kernel_ms": round(rows[0][1] / nchunks, 4),
+                     "kernel_ms_max_rank": round(kmax / nchunks, 4),
+                     "launches_per_step": nchunks,
+                     "algorithmic_bytes_per_launch": int(alg0 / nchunks),
                      "read_frac": round(rb0 / (rows[0][1] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                      "read_frac_per_rank": [x["read_frac"] for x in per_rank]},
-        "pcie_inclusive": {"Mpackets_per_s": round(n / pcie_max / 1e6, 1), "s": round(pcie_max, 3),
-                           "GBps_capture_in": round(dl / pcie_max / 1e9, 2),
-                           "records_per_call": call,
-                           "path": "registered capture -> gpd_decode_pcap_at per call "
-                                   "(raw bytes H2D in 64 MiB chunks, records found in HBM by the "
-                                   "device walk, decode, results D2H into registered result "
-                                   "arrays)"},
         "per_rank": per_rank,
-        "pcie_diag_rank0": pcie_diag,
         "setup_s": {"generate": round(rows[0][7], 2), "locate": round(rows[0][8], 2),
                     "register": round(rows[0][9], 2), "h2d": round(rows[0][10], 2),
                     "index": round(rows[0][11], 2)},
     }
+    if args.full:
+        out["pcie_inclusive"] = {"Mpackets_per_s": round(n / pcie_max / 1e6, 1), "s": round(pcie_max, 3),
+                                 "GBps_capture_in": round(dl / pcie_max / 1e9, 2),
+                                 "records_per_call": call,
+                                 "path": "registered capture -> gpd_decode_pcap_at per call "
+                                         "(raw bytes H2D in 64 MiB chunks, records found in HBM by the "
+                                         "device walk, decode, results D2H into registered result "
+                                         "arrays)"}
+        out["pcie_diag_rank0"] = pcie_diag
+    else:  # the streamed leg did not run: no figures of it
+        for x in per_rank:
+            del x["pcie_inclusive_s"], x["streamed_equals_resident"]
+    if dumped:
+        out["outputs"] = dumped
     return out
 
 
@@ -1190,9 +1267,23 @@ def main():
                     help="tests only: every rank on cuda:0 (the N-rank path on a one-GPU box, gloo)")
     ap.add_argument("--no-probe", action="store_true", help="skip the attainable-bandwidth probe "
                     "(roofline.attainable)")
-    ap.add_argument("--lean", action="store_true", help="only the timed launches (profiling runs: "
-                    "no 36-B record line, no fallback split, no CPU baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, every figure that takes runs of its own: 36-B record "
+                    "and other-result-form launches, fallback split, PCIe-inclusive rate, attainable "
+                    "probe, the other configurations, config 5's streamed leg, CPU baseline "
+                    "(each still switched off by its --no-... option)")
+    ap.add_argument("--lean", action="store_true", help="only the timed launches: what a run "
+                    "without --full does (kept for scripts that pass it; overrides --full)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the results of the last one (a fixed seeded "
+                    "sample of 2^19 packets of a larger batch) to DIR/<name>.npy as float64: index, "
+                    "status, csum (k,), layers, net_hash, tp_hash (k, 2: low and high 32-bit word); "
+                    "rank 0's shard")
     args = ap.parse_args()
+    args.full = args.full and not args.lean
+    if args.dump_outputs and (args.host or "copy" in args.ablate):
+        raise SystemExit("bench: --dump-outputs writes the timed device-resident steps' results "
+                         "(not with --host or --ablate copy)")
     if "nodecode" in args.ablate or "nowait" in args.ablate:
         # the stream-only ablations exist only in the diagnostic library (libgpd_diag.so,
         # -DGPD_DIAG); the shipped libgpd.so refuses their option bits
@@ -1341,6 +1432,9 @@ def main():
     # correctness guard on what was measured (cheap: status classes only)
     st = (dev_res.records.view(torch.int32)[0::8] if aos else dev_res.status).cpu().numpy().view(np.uint32)
     n_err = int(np.count_nonzero((st & 3) != 0))
+    dumped = None
+    if args.dump_outputs and rank == 0:  # what the last timed step wrote (nothing ran since)
+        dumped = dump_outputs(args.dump_outputs, dev_res, n, torch.device("cuda", local))
     out = summarize(workload, n, world, args.steps, args.warmup, elapsed, kern_ms, kern_ms_max,
                     batch, n_err, interleaved=16 if pcap_info else 0)
     out["config"]["result_form"] = "gpd_record (AoS)" if aos else "SoA arrays"
@@ -1348,7 +1442,9 @@ def main():
     out["roofline"]["kernel_ms_method"] = (
         "HIP events on the launch stream around the K timed launches, / K (gaps between launches "
         "included)" if span else "HIP events on the launch stream around each timed launch, mean")
-    if not args.ablate and not args.lean:  # the 36-B record (hdr_off on, as the flow table uses)
+    if dumped:
+        out["outputs"] = dumped
+    if args.full and not args.ablate:  # the 36-B record (hdr_off on, as the flow table uses)
         # the five SoA arrays + hdr_off (the decode -> flow table pipeline's form); gpd_records +
         # hdr_off beside it (gpd_flow_insert takes either; measured slower on this part)
         out["record36"] = bench_record36(parser, dev_batch, n, local, stream, out, args)
@@ -1363,7 +1459,7 @@ def main():
         if world == 1 and batch is not None and not pcap_info:
             # the same batch from host memory (north star: the rate including pinned H2D/D2H)
             out["pcie_inclusive"] = bench_host(parser, batch, n, "registered", 3, 1)
-    if not args.ablate and not args.lean and not args.no_probe:
+    if args.full and not args.ablate and not args.no_probe:
         rf = out["roofline"]
         rf["attainable"] = attainable(n, rf["algorithmic_read_bytes"], local, rf["achieved"], soa=not aos)
     if pcap_info:
@@ -1382,13 +1478,13 @@ def main():
     if args.ablate:
         out["ablation"] = args.ablate
         out["metric"] = "DIAGNOSTIC ablation (not the metric): " + out["metric"]
-    if world == 1 and not args.ablate and not args.lean and not args.no_side and args.config == "udp64":
+    if world == 1 and args.full and not args.ablate and not args.no_side and args.config == "udp64":
         # the other configurations, each timed on its own resident batch (BASELINE.json configs
         # 3, 4 and 5 per GPU, and the north star's 64-B Eth/IPv4/TCP)
         del dev_res
         for c in SIDE_CONFIGS:
             out[c] = bench_side(c, parser, args, local, stream)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.ablate and not args.lean:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.ablate:
         out["cpu_baseline"] = cpu_baseline(batch, args.cpu_budget / 3)
     if rank == 0:
         print(json.dumps(out), flush=True)

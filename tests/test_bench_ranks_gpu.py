@@ -17,7 +17,7 @@ def _bench(*args, gpus=2, timeout=300):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dist-backend",
-                        "gloo", "--same-device", "--no-cpu-baseline", "--settle-ms", "20", *args],
+                        "gloo", "--same-device", "--full", "--no-cpu-baseline", "--settle-ms", "20", *args],
                        capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
