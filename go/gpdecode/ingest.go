@@ -1,6 +1,6 @@
 package gpdecode
 
-// Ingest and flow-table wrappers over include/gpd_pcap.h, include/gpd_afpacket.h and
+// Ingest and flow-table wrappers over include/gpd_pcap.h, include/gpd_pcapng.h, include/gpd_afpacket.h and
 // include/gpd_flow.h.  Like gpdecode.go this file is not compiled here (no Go toolchain);
 // tests/c/abi_host.c drives the same C calls from a plain C host and checks them.
 
@@ -11,6 +11,7 @@ package gpdecode
 #include <hip/hip_runtime_api.h>
 #include "gpd.h"
 #include "gpd_pcap.h"
+#include "gpd_pcapng.h"
 #include "gpd_afpacket.h"
 #include "gpd_flow.h"
 */
@@ -91,6 +92,111 @@ func (p *BatchDecodingLayerParser) DecodeCapture(capture []byte, maxPackets int)
 		return nil, 0, lastError("gpd_decode_pcap", rc)
 	}
 	return r, int(pos), nil
+}
+
+// NgOptions is pcapgo.NgReaderOptions (pcapgo/ngread.go:22-36) without the callbacks, plus the
+// library's own knobs (gpd_pcapng_opts).
+type NgOptions struct {
+	WantMixedLinkType          bool
+	ErrorOnMismatchingLinkType bool
+	SkipUnknownVersion         bool
+	HostWalk                   bool   // device_walk = 0: the block walk on the host
+	ChunkBytes                 uint64 // 0: 64 MiB
+}
+
+// NgCapture is pcapgo.NgReader (pcapgo/ngread.go:42-58) over a pcapng capture already in
+// memory.  The capture must stay alive and unmoved until Close (mmap'ed, or C memory).
+type NgCapture struct {
+	r       *C.gpd_pcapng_reader
+	capture []byte
+}
+
+func b2u(b bool) C.uint32_t {
+	if b {
+		return 1
+	}
+	return 0
+}
+
+// NewNgCapture is pcapgo.NewNgReader (pcapgo/ngread.go:61-83): the first section header and,
+// unless WantMixedLinkType, the section's first interface are read; the error is the
+// reference's ("Unknown magic %x", ErrNgVersionMismatch's text, io.EOF's, ...).
+func NewNgCapture(capture []byte, o NgOptions) (*NgCapture, error) {
+	opts := C.gpd_pcapng_opts{
+		want_mixed_linktype:           b2u(o.WantMixedLinkType),
+		error_on_mismatching_linktype: b2u(o.ErrorOnMismatchingLinkType),
+		skip_unknown_version:          b2u(o.SkipUnknownVersion),
+		device_walk:                   -1,
+		chunk_bytes:                   C.uint64_t(o.ChunkBytes),
+	}
+	if o.HostWalk {
+		opts.device_walk = 0
+	}
+	ng := &NgCapture{capture: capture}
+	var stop C.int
+	rc := C.gpd_pcapng_open((*C.uint8_t)(bytesPtr(capture)), C.uint64_t(len(capture)), &opts, &ng.r, &stop)
+	if rc != C.GPD_OK {
+		return nil, errors.New(C.GoString(C.gpd_pcapng_last_error()))
+	}
+	return ng, nil
+}
+
+// LinkType is NgReader.LinkType() (pcapgo/ngread.go:578-580).
+func (ng *NgCapture) LinkType() layers.LinkType { return layers.LinkType(C.gpd_pcapng_linktype(ng.r)) }
+
+// NInterfaces is NgReader.NInterfaces() (pcapgo/ngread.go:596-598).
+func (ng *NgCapture) NInterfaces() int { return int(C.gpd_pcapng_ninterfaces(ng.r)) }
+
+// SkipSection is NgReader.SkipSection() (pcapgo/ngread.go:286-292).
+func (ng *NgCapture) SkipSection() error {
+	if rc := C.gpd_pcapng_skip_section(ng.r, nil); rc != C.GPD_OK {
+		return errors.New(C.GoString(C.gpd_pcapng_last_error()))
+	}
+	return nil
+}
+
+// Close releases the reader (not the capture).
+func (ng *NgCapture) Close() {
+	C.gpd_pcapng_close(ng.r)
+	ng.r = nil
+}
+
+// DecodeNgCapture replaces
+//
+//	r, _ := pcapgo.NewNgReader(f, options)
+//	for { data, _, err := r.ReadPacketData(); ...; parser.DecodeLayers(data, &decoded) }
+//
+// (pcapgo/ngread.go:443-545 feeding parser.go:277-317): the capture's next maxPackets packets
+// are found by the block walk on the device and decoded where they lie.  The call is
+// continuable: the next one goes on behind the last packet returned.  err is nil at the limit,
+// io.EOF when the capture ended where a block would start, else the reference's text for the
+// block the reader stopped at (the packets before it are decoded and counted in the Result).
+func (p *BatchDecodingLayerParser) DecodeNgCapture(ng *NgCapture, maxPackets int) (*Result, error) {
+	if err := p.configure(); err != nil {
+		return nil, err
+	}
+	if maxPackets <= 0 {
+		return newResult(0), nil
+	}
+	r := newResult(maxPackets)
+	out := r.cResult()
+	var pn runtime.Pinner // out (Go memory) points into r's slices
+	defer pn.Unpin()
+	r.pin(&pn)
+	var n C.uint64_t
+	var stop C.int
+	rc := C.gpd_decode_pcapng(p.ctx, ng.r, C.uint64_t(maxPackets), &out, &n, &stop, 0)
+	runtime.KeepAlive(ng.capture)
+	r.truncate(int(n))
+	switch {
+	case rc == C.GPD_ERR_PCAPNG:
+		return r, errors.New(C.GoString(C.gpd_pcapng_last_error()))
+	case rc != C.GPD_OK:
+		return nil, lastError("gpd_decode_pcapng", rc)
+	case stop == C.GPD_PCAPNG_STOP_EOF:
+		return r, io.EOF
+	}
+	return r, nil
 }
 
 // Ring is a mapped TPACKET_V3 ring (afpacket options.go blockSize/numBlocks).  The Go side

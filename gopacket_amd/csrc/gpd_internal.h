@@ -136,6 +136,31 @@ struct PwArgs {
 hipError_t launch_pcap_walk(const PwArgs &A, hipStream_t stream);
 hipError_t launch_pcap_fill(const PwArgs &A, hipStream_t stream);
 
+// The pcapng block walk on the GPU (gpd_ngwalk.hip): one chunk of capture bytes in HBM, between
+// two blocks that change the reader's state.  The control block is a PwCtl whose status also
+// says where the device stopped short on purpose: kNgTailState / kNgTailBlock with `n` the
+// packets before and `next` the position of the block the host reads on from.
+constexpr uint32_t kNgMaxIfaces = 32;     // interfaces the chunk state holds (more: the host walks)
+constexpr uint32_t kNgTailState = 32;     // PwCtl::status: stopped at a section header, interface
+                                          // description or statistics block
+constexpr uint32_t kNgTailBlock = 64;     // ... at a block the device does not vouch for
+struct NgArgs {
+  const uint8_t *d;        // the chunk's bytes in HBM
+  uint32_t T;              // bytes there
+  uint32_t own_end;        // blocks whose headers start before this are the chunk's
+  uint32_t nseg;           // ceil(own_end / kPwSeg)
+  uint32_t nif;            // interfaces of the section so far (<= kNgMaxIfaces)
+  uint32_t keep;           // bit i: interface i has the first interface's link type
+  uint32_t snaplen0;       // interface 0's snap length (simple packet blocks)
+  bool be, last;           // the section's byte order; the chunk ends the capture (T = its end)
+  bool drop_is_error;      // ErrorOnMismatchingLinkType: a packet to drop is the host's
+  PwCtl *ctl, *ctl_next;   // this chunk's block; the next chunk's (its entry is written)
+  uint32_t *st, *ex, *ct, *bad, *base;  // per segment
+  uint32_t *off, *len;     // per packet: data offset, capture length
+};
+hipError_t launch_ng_walk(const NgArgs &A, hipStream_t stream);
+hipError_t launch_ng_fill(const NgArgs &A, hipStream_t stream);
+
 // The TPACKET_V3 block walk on the GPU (gpd_tpv3walk.hip): one group of consecutive ring
 // blocks in HBM, one workgroup per block.
 constexpr uint32_t kTwWin = 32768;           // LDS window of a block's bytes

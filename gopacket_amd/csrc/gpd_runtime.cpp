@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "gpd_internal.h"
+#include "gpd_pcapng_internal.h"
 
 namespace {
 
@@ -1607,6 +1608,306 @@ void gpd_decode_pcap_last_times(double *ms6) {
   ms6[3] = g_pt_stage;     // descriptor rebase, staging copies, issuing transfers and launches
   ms6[4] = g_pt_sync;      // waiting for a slot's transfers and decode
   ms6[5] = g_pt_drain;     // copying a slot's results out (none with registered result arrays)
+}
+
+}  // extern "C"
+
+// ---- pcapng capture in host memory (include/gpd_pcapng.h): raw-byte chunks H2D -> block walk
+// on the device -> decode -> D2H, between the blocks that change the reader's state ----
+namespace {
+
+thread_local uint32_t g_ng_counts[8];
+
+enum NgHow { kNgLimit, kNgEof, kNgState, kNgBlock, kNgHostChunk };
+
+// The reader's next packets (at most lim) through the sequential host walk, decoded with
+// gpd_decode_host in batches.  *k: packets decoded; *st: the GPD_PCAPNG_STOP_* of the walk.
+int ng_decode_host_walk(gpd_ctx *ctx, gpd_pcapng_reader *r, uint64_t lim, const gpd_result *out, uint64_t *k,
+                        int *st) {
+  thread_local std::vector<uint32_t> off, cap;
+  constexpr uint64_t kBatch = 1u << 20;
+  *k = 0;
+  *st = GPD_PCAPNG_STOP_LIMIT;
+  while (*k < lim && *st == GPD_PCAPNG_STOP_LIMIT) {
+    const uint64_t m = std::min(lim - *k, kBatch);
+    if (off.size() < m) {
+      off.resize(m);
+      cap.resize(m);
+    }
+    uint64_t n = 0;
+    const int rc = gpd_pcapng_index(r, m, off.data(), cap.data(), nullptr, nullptr, nullptr, nullptr, nullptr, &n, st);
+    if (rc != GPD_OK && rc != GPD_ERR_PCAPNG) return rc;
+    if (n) {
+      gpd_batch b{r->buf, r->len, off.data(), cap.data(), n};
+      gpd_result o = *out;
+      auto sh = [&](auto *p) { return p ? p + *k : p; };
+      o.status = sh(out->status);
+      o.layers = sh(out->layers);
+      o.net_hash = sh(out->net_hash);
+      o.tp_hash = sh(out->tp_hash);
+      o.csum = sh(out->csum);
+      o.hdr_off = sh(out->hdr_off);
+      o.detail = sh(out->detail);
+      const int rd = gpd_decode_host(ctx, &b, &o);
+      if (rd) return rd;
+      *k += n;
+    }
+  }
+  return GPD_OK;
+}
+
+// The device walk from the reader's position while no block changes its state: at most max_n
+// packets decoded into `out`.  *how tells why it returned and the reader stands accordingly:
+//   kNgLimit      max_n packets done; the reader at the block after the last of them
+//   kNgEof        the capture ended exactly after a block (the reader is stopped: EOF)
+//   kNgState      at a section header, interface description or statistics block
+//   kNgBlock      at a block the device does not vouch for
+//   kNgHostChunk  at the entry of a chunk the device gave up (*chunk_end: where that chunk ends)
+int ng_device_walk(gpd_ctx *ctx, gpd_pcapng_reader *r, uint64_t max_n, const gpd_result *out, int nthreads,
+                   uint64_t *handled, NgHow *how, uint64_t *chunk_end) {
+  const uint8_t *buf = r->buf;
+  const uint64_t len = r->len;
+  const uint64_t chunk = r->opts.chunk_bytes ? r->opts.chunk_bytes : (uint64_t)gpd::kPwSeg * gpd::kPwMaxSeg;
+  constexpr uint64_t margin = 128u << 10;             // a block may run this far past its chunk
+  const uint64_t cap_pkts = (chunk + margin) / 16 + 64;  // a packet block takes 16 bytes or more
+  *handled = 0;
+  const bool be = r->big_endian;
+  auto rd = [&](uint64_t p) {
+    uint32_t v;
+    std::memcpy(&v, buf + p, 4);
+    return be ? __builtin_bswap32(v) : v;
+  };
+  // the mean block size (the decode's staging choices): the first blocks, read here
+  uint64_t mean = 96;
+  {
+    uint64_t p = r->pos, nb = 0;
+    while (nb < 64 && p + 12 <= len) {
+      const uint32_t total = rd(p + 4);
+      if (total < 12 || (total & 3) || p + total > len) break;
+      p += total;
+      nb++;
+    }
+    if (nb) mean = std::max<uint64_t>(16, (p - r->pos) / nb);
+  }
+  int rc = alloc_slots(ctx, std::max<uint64_t>(ctx->slot_bytes, chunk + margin + 64),
+                       std::max<uint64_t>(ctx->slot_pkts, cap_pkts), false, out->detail != nullptr);
+  if (rc) return rc;
+  SlotGuard guard{ctx};
+  // the chunk state: what the walk needs of the reader's, constant until a state-changing block
+  gpd::NgArgs S{};
+  S.nif = (uint32_t)r->ifaces.size();
+  for (uint32_t i = 0; i < S.nif; i++)
+    if (r->ifaces[i].linktype == r->linktype) S.keep |= 1u << i;
+  S.snaplen0 = S.nif ? r->ifaces[0].snaplen : 0;
+  S.be = be;
+  S.drop_is_error = r->opts.error_on_mismatching_linktype != 0;
+  auto issue = [&](int k, uint64_t B, uint64_t entry0, bool first) -> int {
+    auto &s = ctx->slot[k & 1];
+    if (s.busy) {
+      HIP_TRY(hipStreamSynchronize(s.stream));
+      drain_slot(s, out);
+      s.busy = false;
+    }
+    const uint64_t own = std::min<uint64_t>(chunk, len - B);
+    const uint64_t T = std::min<uint64_t>(own + margin, len - B);
+    const bool last = B + own >= len;
+    const uint8_t *src = buf + B;
+    if (!ctx->is_registered(src, T)) {
+      HIP_TRY(hipStreamSynchronize(s.stream));  // (its staging buffer may still be read)
+      par_memcpy(s.h_data, src, T, nthreads);
+      src = s.h_data;
+    }
+    gpd::PwCtl *dc = ctx->d_pw_ctl + (k & 1), *hc = ctx->h_pw_ctl + (k & 1);
+    HIP_TRY(hipMemcpyAsync(s.d_data, src, T, hipMemcpyHostToDevice, s.stream));
+    if (first) {
+      hc->entry = (uint32_t)entry0;
+      HIP_TRY(hipMemcpyAsync(&dc->entry, &hc->entry, 4, hipMemcpyHostToDevice, s.stream));
+    } else {
+      HIP_TRY(hipStreamWaitEvent(s.stream, ctx->ev_pw[(k - 1) & 1], 0));
+    }
+    gpd::NgArgs A = S;
+    A.d = s.d_data;
+    A.T = (uint32_t)T;
+    A.own_end = (uint32_t)own;
+    A.nseg = (uint32_t)((own + gpd::kPwSeg - 1) / gpd::kPwSeg);
+    A.last = last;
+    A.ctl = dc;
+    A.ctl_next = last ? nullptr : ctx->d_pw_ctl + ((k + 1) & 1);
+    A.st = s.d_pw;
+    A.ex = s.d_pw + gpd::kPwMaxSeg;
+    A.ct = s.d_pw + 2 * gpd::kPwMaxSeg;
+    A.bad = s.d_pw + 3 * gpd::kPwMaxSeg;
+    A.base = s.d_pw + 4 * gpd::kPwMaxSeg;
+    A.off = s.d_off;
+    A.len = s.d_len;
+    hipError_t e = gpd::launch_ng_walk(A, s.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hc, dc, sizeof(gpd::PwCtl), hipMemcpyDeviceToHost, s.stream);
+    if (e == hipSuccess) e = hipEventRecord(ctx->ev_pw[k & 1], s.stream);
+    if (e == hipSuccess) e = gpd::launch_ng_fill(A, s.stream);
+    if (e != hipSuccess) return set_err(GPD_ERR_HIP, "gpd_decode_pcapng: device walk: %s", hipGetErrorString(e));
+    gpd_batch b{s.d_data, T, s.d_off, s.d_len, cap_pkts};
+    gpd_result res{s.d_status, s.d_layers, s.d_nh, s.d_th, s.d_csum, nullptr, out->hdr_off ? s.d_hoff : nullptr,
+                   nullptr, out->detail ? s.d_det : nullptr};
+    return launch(ctx, &b, &res, s.stream, false, &dc->n, std::max<uint64_t>(1, own / mean));
+  };
+  uint64_t B = r->pos & ~15ull;  // chunk base (16-byte aligned: the decoder's batch buffer)
+  uint64_t entry = r->pos - B;   // its first block header
+  uint64_t done = 0;
+  *how = kNgLimit;
+  rc = issue(0, B, entry, true);
+  if (rc) return rc;
+  for (int k = 0;; k++) {
+    auto &s = ctx->slot[k & 1];
+    const uint64_t own = std::min<uint64_t>(chunk, len - B);
+    const bool last = B + own >= len;
+    // queue the next chunk now unless this one should end the call (its packets, estimated
+    // from the mean block size, cover what is left)
+    const bool ahead = !last && done + own / mean < max_n;
+    if (ahead && (rc = issue(k + 1, B + own, 0, false))) return rc;
+    HIP_TRY(hipEventSynchronize(ctx->ev_pw[k & 1]));  // chunk k walked: its count
+    const gpd::PwCtl c = ctx->h_pw_ctl[k & 1];
+    g_ng_counts[0]++;
+    g_ng_counts[7] += c.pad[0];
+    if (c.status & 1u) {  // the host walks this chunk from its entry (its decode saw 0 packets)
+      g_ng_counts[1]++;
+      g_ng_counts[3] += (c.status >> 1) & 1u;
+      g_ng_counts[5] += (c.status >> 3) & 1u;
+      g_ng_counts[6] += (c.status >> 4) & 1u;
+      r->pos = B + entry;
+      *chunk_end = B + own;
+      *how = kNgHostChunk;
+      break;
+    }
+    const uint64_t take = std::min<uint64_t>(c.n, max_n - done);
+    hipError_t e = results_d2h(ctx, s, out, done, take, s.stream);
+    if (e != hipSuccess) return set_err(GPD_ERR_HIP, "gpd_decode_pcapng: D2H: %s", hipGetErrorString(e));
+    s.lo = done;
+    s.hi = done + take;
+    s.busy = take > 0;
+    done += take;
+    if (take < c.n) {  // the bound falls inside this chunk: the reader walks to it from the entry
+      r->pos = B + entry;
+      gpd::NgPacket p;
+      for (uint64_t i = 0; i < take; i++)
+        if (r->next_packet(&p)) return set_err(GPD_ERR_INVALID, "gpd_decode_pcapng: host and device walks disagree");
+      *how = kNgLimit;
+      break;
+    }
+    r->pos = B + c.next;
+    if (done == max_n) {
+      *how = kNgLimit;
+      break;
+    }
+    if (c.status & (gpd::kNgTailState | gpd::kNgTailBlock)) {
+      g_ng_counts[2]++;
+      g_ng_counts[4] += (c.status & gpd::kNgTailBlock) != 0;
+      *how = (c.status & gpd::kNgTailState) ? kNgState : kNgBlock;
+      break;
+    }
+    if (last) {  // status 0 on the last chunk: the walk ended exactly at the capture's end
+      *how = kNgEof;
+      break;
+    }
+    entry = c.next - own;
+    B += own;
+    if (!ahead && (rc = issue(k + 1, B, 0, false))) return rc;
+  }
+  for (auto &s : ctx->slot) {  // (a chunk queued ahead and not needed is waited for and dropped)
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    if (s.busy) {
+      drain_slot(s, out);
+      s.busy = false;
+    }
+  }
+  *handled = done;
+  return GPD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpd_decode_pcapng(gpd_ctx *ctx, gpd_pcapng_reader *r, uint64_t max_n, const gpd_result *out, uint64_t *n_out,
+                      int *stop, int nthreads) {
+  if (!ctx || !r || !out || !out->status || !out->layers || !n_out)
+    return set_err(GPD_ERR_INVALID, "gpd_decode_pcapng: null argument");
+  if (out->ext) return set_err(GPD_ERR_INVALID, "gpd_decode_pcapng: ext records not supported");
+  if (out->records) return set_err(GPD_ERR_INVALID, "gpd_decode_pcapng: results as SoA arrays only");
+  if (r->opts.want_mixed_linktype)
+    return set_err(GPD_ERR_INVALID, "gpd_decode_pcapng: a reader with want_mixed_linktype (a context has one first layer)");
+  if (nthreads <= 0) nthreads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  for (auto &c : g_ng_counts) c = 0;
+  *n_out = 0;
+  if (stop) *stop = GPD_PCAPNG_STOP_LIMIT;
+  if (max_n == 0) return GPD_OK;
+  gpd::DeviceScope dscope_;
+  HIP_TRY(dscope_.set(ctx->device));
+  uint64_t done = 0;
+  auto shifted = [&](uint64_t d) {
+    gpd_result o = *out;
+    auto sh = [&](auto *p) { return p ? p + d : p; };
+    o.status = sh(out->status);
+    o.layers = sh(out->layers);
+    o.net_hash = sh(out->net_hash);
+    o.tp_hash = sh(out->tp_hash);
+    o.csum = sh(out->csum);
+    o.hdr_off = sh(out->hdr_off);
+    o.detail = sh(out->detail);
+    return o;
+  };
+  auto finish = [&](int st) {
+    *n_out = done;
+    if (stop) *stop = st;
+    return r->result(st);
+  };
+  const bool dw = r->opts.device_walk != 0;
+  for (;;) {
+    if (r->stop) return finish(r->stop);
+    if (done == max_n) return finish(GPD_PCAPNG_STOP_LIMIT);
+    uint64_t lim = max_n - done;  // packets the host walk takes next
+    uint64_t until = UINT64_MAX;  // ... or until the reader stands here
+    // (state-changing blocks right here are the reader's: no chunk travels only to stop at them)
+    if (dw && r->absorb_state_blocks()) continue;
+    if (dw && r->ifaces.size() <= gpd::kNgMaxIfaces && r->pos < r->len) {
+      uint64_t handled = 0, chunk_end = 0;
+      NgHow how = kNgLimit;
+      const gpd_result o = shifted(done);
+      const int rc = ng_device_walk(ctx, r, max_n - done, &o, nthreads, &handled, &how, &chunk_end);
+      done += handled;
+      *n_out = done;
+      if (rc) return rc;
+      if (how == kNgLimit) continue;
+      if (how == kNgEof) {
+        r->pos = r->blk_pos = r->len;
+        r->stop = GPD_PCAPNG_STOP_EOF;
+        r->err = "EOF";
+        continue;
+      }
+      if (how == kNgState) {  // the reader takes the state-changing blocks; the device goes on behind them
+        r->absorb_state_blocks();
+        continue;
+      }
+      if (how == kNgBlock) lim = 1;
+      if (how == kNgHostChunk) until = chunk_end;
+    }
+    // The host walk: all of the call without the device walk; else the one packet behind a
+    // block the device does not vouch for, or the chunk it gave up, and then the device again.
+    while (lim && !r->stop && r->pos < until) {
+      const gpd_result o = shifted(done);
+      uint64_t k = 0;
+      int st = GPD_PCAPNG_STOP_LIMIT;
+      const int rc = ng_decode_host_walk(ctx, r, std::min<uint64_t>(lim, until == UINT64_MAX ? lim : 256), &o, &k, &st);
+      done += k;
+      lim -= k;
+      *n_out = done;
+      if (rc) return rc;
+    }
+  }
+}
+
+void gpd_decode_pcapng_last_walk_counts(uint32_t *c8) {
+  if (!c8) return;
+  for (int k = 0; k < 8; k++) c8[k] = g_ng_counts[k];
 }
 
 }  // extern "C"

@@ -573,6 +573,39 @@ class DecodingLayerParser:
             check(rc, "gpd_decode_pcap_at")
         return n.value, nxt.value, stop.value, err
 
+    def DecodePcapNg(self, cap, options=None, max_n: Optional[int] = None, nthreads: int = 0,
+                     out: Optional[BatchResult] = None, detail: bool = False):
+        """A pcapng capture through gpd_decode_pcapng: raw capture bytes chunked host -> device,
+        the block walk on the device (options.device_walk = 0: on the host), decoded where they
+        lie, results back.  `cap` is a capture array (pcap.capture_array) or an open
+        pcapng.NgReader; with a reader and max_n the call is continuable: each call decodes the
+        reader's next max_n packets.  Returns (BatchResult of the decoded packets, their number,
+        STOP_* of pcapng, error text or None — the ReadPacketData loop's stop,
+        pcapgo/ngread.go:443-545).  `out` (a BatchResult with hdr_off, at least max_n entries)
+        is reused when given."""
+        from . import pcapng
+        rd = cap if isinstance(cap, pcapng.NgReader) else pcapng.NgReader(cap, options)
+        m = max(0, rd.data_len - rd.pos()) // 12 + 1 if max_n is None else int(max_n)
+        if out is not None:
+            if len(out.status) < m or out.hdr_off is None:
+                raise ValueError("DecodePcapNg: out must hold max_n entries, with hdr_off")
+            res = out
+        else:
+            res = BatchResult(np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint64),
+                              np.zeros(m, np.uint64), np.zeros(m, np.uint32), None,
+                              np.zeros(m, np.uint32), np.zeros(m, DETAIL_DTYPE) if detail else None)
+        r = _c_result(res)
+        n, stop = C.c_uint64(), C.c_int()
+        rc = pcapng.ng_lib().gpd_decode_pcapng(self.ctx().h, rd.h, m, C.byref(r), C.byref(n), C.byref(stop),
+                                               int(nthreads))
+        err = None
+        if rc == pcapng.GPD_ERR_PCAPNG:
+            err = lib.gpd_last_error_string().decode()
+        elif rc != 0:
+            check(rc, "gpd_decode_pcapng")
+        k = n.value
+        return _head(res, k), k, stop.value, err
+
     def DecodeTPv3(self, ring, max_n: int = 1 << 20, max_blocks: Optional[int] = None,
                    add_vlan_header: bool = False, nthreads: int = 0, out=None, ci=None,
                    detail: bool = False):
