@@ -109,54 +109,55 @@ constexpr uint32_t kMaxFastWavesPerCU = 4 * 8 * 4;
 // fb_wcount).
 bool fast_eligible(const KParams &P);
 
-// The pcap record walk on the GPU (gpd_pcapwalk.hip): one chunk of capture bytes in HBM.
+// The segmented walk of a capture chunk in HBM (gpd_segwalk.h), shared by the pcap record walk
+// and the pcapng block walk.
 constexpr uint32_t kPwSeg = 2048;        // bytes per walking lane
 constexpr uint32_t kPwMaxSeg = 1u << 15; // segments per chunk (64 MiB)
 struct PwCtl {       // a chunk's control block (device; copied back to the host)
-  uint32_t entry;    // in: its first record header (relative to the chunk)
-  uint32_t n;        // out: records whose headers start in [entry, own_end)
-  uint32_t next;     // out: the first record header at or past own_end
-  uint32_t status;   // out: 0, or 1 | reasons (2 speculation refuted, 4 rejected record, 8 header
-                     // not covered, 16 walk ends short) = the host walks from `entry` (gpd_pcapwalk.hip)
+  uint32_t entry;    // in: its first header (relative to the chunk)
+  uint32_t n;        // out: packets whose headers start in [entry, own_end), or before a stop
+  uint32_t next;     // out: the first header at or past own_end, or the one the walk stopped at
+  uint32_t status;   // out: 0; or 1 | reasons (2 speculation refuted, 4 rejected record, 8 header
+                     // not covered, 16 walk ends short) = the host walks from `entry`; or, bit 0
+                     // clear, the stop kind of a format that keeps the packets before a stop
+                     // (kNgTailState / kNgTailBlock)
   uint32_t miss_st;  // out (diagnostic): the first refuted speculation's start ...
   uint32_t miss_at;  // ... and its segment (kNone: none)
   uint32_t pad[2];   // [0]: segments the stitch re-walked from the true walk's position
+                     // [1]: the segment whose stop ended the walk (kNone: none), for the fill
 };
-struct PwArgs {
+struct SegArgs {           // what the walk needs whatever the format
   const uint8_t *d;        // the chunk's bytes in HBM
   uint32_t T;              // bytes there
-  uint32_t own_end;        // records whose headers start before this are the chunk's
+  uint32_t own_end;        // packets whose headers start before this are the chunk's
   uint32_t nseg;           // ceil(own_end / kPwSeg)
-  uint32_t snaplen;
-  bool be, nano, last;     // header byte order, ns timestamps; the chunk ends the capture (T = its end)
+  bool last;               // the chunk ends the capture (T = its end)
   PwCtl *ctl, *ctl_next;   // this chunk's block; the next chunk's (its entry is written)
   uint32_t *st, *ex, *ct, *bad, *base;  // per segment
-  uint32_t *off, *len;     // per record: data offset, capture length
+  uint32_t *off, *len;     // per packet: data offset, capture length
+};
+
+// The pcap record walk on the GPU (gpd_pcapwalk.hip).
+struct PwArgs : SegArgs {
+  uint32_t snaplen;
+  bool be, nano;           // header byte order, ns timestamps
 };
 hipError_t launch_pcap_walk(const PwArgs &A, hipStream_t stream);
 hipError_t launch_pcap_fill(const PwArgs &A, hipStream_t stream);
 
-// The pcapng block walk on the GPU (gpd_ngwalk.hip): one chunk of capture bytes in HBM, between
-// two blocks that change the reader's state.  The control block is a PwCtl whose status also
-// says where the device stopped short on purpose: kNgTailState / kNgTailBlock with `n` the
-// packets before and `next` the position of the block the host reads on from.
+// The pcapng block walk on the GPU (gpd_ngwalk.hip): a chunk between two blocks that change the
+// reader's state.  Its stops keep the packets before them: status kNgTailState / kNgTailBlock
+// with `n` the packets before and `next` the position of the block the host reads on from.
 constexpr uint32_t kNgMaxIfaces = 32;     // interfaces the chunk state holds (more: the host walks)
 constexpr uint32_t kNgTailState = 32;     // PwCtl::status: stopped at a section header, interface
                                           // description or statistics block
 constexpr uint32_t kNgTailBlock = 64;     // ... at a block the device does not vouch for
-struct NgArgs {
-  const uint8_t *d;        // the chunk's bytes in HBM
-  uint32_t T;              // bytes there
-  uint32_t own_end;        // blocks whose headers start before this are the chunk's
-  uint32_t nseg;           // ceil(own_end / kPwSeg)
+struct NgArgs : SegArgs {
   uint32_t nif;            // interfaces of the section so far (<= kNgMaxIfaces)
   uint32_t keep;           // bit i: interface i has the first interface's link type
   uint32_t snaplen0;       // interface 0's snap length (simple packet blocks)
-  bool be, last;           // the section's byte order; the chunk ends the capture (T = its end)
+  bool be;                 // the section's byte order
   bool drop_is_error;      // ErrorOnMismatchingLinkType: a packet to drop is the host's
-  PwCtl *ctl, *ctl_next;   // this chunk's block; the next chunk's (its entry is written)
-  uint32_t *st, *ex, *ct, *bad, *base;  // per segment
-  uint32_t *off, *len;     // per packet: data offset, capture length
 };
 hipError_t launch_ng_walk(const NgArgs &A, hipStream_t stream);
 hipError_t launch_ng_fill(const NgArgs &A, hipStream_t stream);

@@ -284,12 +284,6 @@ static void par_for(uint64_t n, uint64_t grain, F fn) {
   for (auto &x : th) x.join();
 }
 
-static void par_memcpy(void *dst, const void *src, uint64_t bytes) {
-  par_for(bytes, 4u << 20, [&](uint64_t lo, uint64_t hi) {
-    std::memcpy(static_cast<uint8_t *>(dst) + lo, static_cast<const uint8_t *>(src) + lo, hi - lo);
-  });
-}
-
 namespace gpd {
 int ctx_device(const gpd_ctx *ctx) { return ctx->device; }
 int ctx_num_cus(const gpd_ctx *ctx) { return ctx->num_cus; }
@@ -1015,7 +1009,9 @@ int gpd_decode_host(gpd_ctx *ctx, const gpd_batch *in, const gpd_result *out) {
       if (ctx->is_registered(in->data + lo16, bytes)) {
         HIP_TRY(hipMemcpyAsync(s.d_data, in->data + lo16, bytes, hipMemcpyHostToDevice, s.stream));
       } else {
-        par_memcpy(s.h_data, in->data + lo16, bytes);
+        par_for(bytes, 4u << 20, [&](uint64_t a, uint64_t b) {
+          std::memcpy(s.h_data + a, in->data + lo16 + a, b - a);
+        });
         HIP_TRY(hipMemcpyAsync(s.d_data, s.h_data, bytes, hipMemcpyHostToDevice, s.stream));
       }
     } else {
@@ -1160,6 +1156,20 @@ static void par_memcpy(uint8_t *dst, const uint8_t *src, uint64_t n, int nthread
     th.emplace_back([=] { std::memcpy(dst + lo, src + lo, hi - lo); });
   }
   for (auto &t : th) t.join();
+}
+
+// `out` with every result array moved on by d packets
+static gpd_result shifted(const gpd_result *out, uint64_t d) {
+  gpd_result r = *out;
+  auto sh = [&](auto *p) { return p ? p + d : p; };
+  r.status = sh(out->status);
+  r.layers = sh(out->layers);
+  r.net_hash = sh(out->net_hash);
+  r.tp_hash = sh(out->tp_hash);
+  r.csum = sh(out->csum);
+  r.hdr_off = sh(out->hdr_off);
+  r.detail = sh(out->detail);
+  return r;
 }
 
 // Host-clock phases of this thread's last gpd_decode_pcap(_at) call (gpd_decode_pcap_last_times).
@@ -1335,42 +1345,40 @@ static int decode_pcap_host_walk(gpd_ctx *ctx, const uint8_t *buf, uint64_t len,
   return GPD_OK;
 }
 
-// The pcap path with the record walk on the device (gpd_pcapwalk.hip): the capture travels
-// in fixed chunks of 64 MiB (plus the longest record past them) on two slots, each chunk's
-// records are found in HBM (the walk of chunk k waits for chunk k-1's, which hands it its
-// first record header), decoded there, and their results copied back.  The host reads one
-// 16-byte control block per chunk: how many records it held and whether the device walk
-// stood (status 0).  *handled records were decoded; *resume is the record header where the
-// host walk must take over (a chunk with status 1: a rejected record, a partial record at
-// the end, a speculation the walk missed), UINT64_MAX when the call is complete.
-static int decode_device_walk(gpd_ctx *ctx, const uint8_t *buf, uint64_t len, const gpd_pcap_info &I,
-                                   uint64_t pos, uint64_t max_n, const gpd_result *out, int nthreads,
-                                   uint64_t *handled, uint64_t *resume, uint64_t *next_pos, int *stop,
-                                   bool *ineligible) {
-  constexpr uint64_t kChunk = (uint64_t)gpd::kPwSeg * gpd::kPwMaxSeg;
-  const uint64_t margin = (16ull + I.snaplen + 31ull) & ~15ull;  // the longest record past a chunk
-  const uint64_t cap_pkts = kChunk / GPD_PCAP_RECORD_BYTES;       // records a chunk can hold
+}  // extern "C"
+
+// The chunk pipeline of the device walks (gpd_segwalk.h; pcap and pcapng): the capture travels
+// in fixed byte chunks (plus a margin: the longest record or block past them) on two slots,
+// each chunk's packets are found in HBM (the walk of chunk k waits for chunk k-1's, which hands
+// it its first header), decoded there, and their results copied back.  The host reads one
+// control block per chunk: how many packets it held and how its walk ended.
+template <class Args>
+struct SegFormat {
+  const char *what;                // the error texts' prefix
+  uint64_t chunk, margin;          // bytes a chunk owns; bytes past them that travel with it
+  uint64_t cap_pkts;               // packets a chunk can hold
+  uint64_t mean;                   // the mean record or block size (the decode's staging choices)
+  Args state;                      // the format's fields (the chunk's are filled in here)
+  hipError_t (*walk)(const Args &, hipStream_t);
+  hipError_t (*fill)(const Args &, hipStream_t);
+};
+struct SegChunk {                  // a walked chunk, as the format's on_chunk sees it
+  gpd::PwCtl c;                    // its control block
+  uint64_t B, entry, own;          // its base, its first header (relative), the bytes it owns
+  bool last;                       // it ends the capture
+  uint64_t take, done;             // packets taken from it; packets taken so far, those included
+  gpd_ctx::Slot *slot;             // where its arrays lie
+};
+// Walks from `pos` until on_chunk(chunk, &more) leaves `more` false (or fails); on_chunk sees
+// every walked chunk after its results (none when the chunk is the host's: status & 1) are on
+// their way back.  *handled packets were decoded into `out`.
+template <class Args, class OnChunk>
+static int seg_device_walk(gpd_ctx *ctx, const uint8_t *buf, uint64_t len, uint64_t pos, uint64_t max_n,
+                           const gpd_result *out, int nthreads, const SegFormat<Args> &F, OnChunk on_chunk,
+                           uint64_t *handled) {
   *handled = 0;
-  *resume = pos;
-  // (records that long, or a capture whose first records cannot be indexed: the host walk,
-  // for the rest of the call — *ineligible)
-  *ineligible = true;
-  if (I.snaplen > (16u << 20)) return GPD_OK;
-  // the mean record size (the decode's staging choices): the first records, walked here
-  uint64_t mean = 96;
-  {
-    uint64_t sp[64];
-    uint32_t sc[64];
-    gpd::PcapOut o;
-    o.pos64 = sp;
-    o.cap = sc;
-    gpd::PcapResult R;
-    if (gpd::pcap_index_flat(buf, len, I, pos, 64, 1, o, R) != GPD_OK || R.n == 0) return GPD_OK;
-    mean = std::max<uint64_t>(16, (R.next_pos - pos) / R.n);
-  }
-  *ineligible = false;
-  int rc = alloc_slots(ctx, std::max<uint64_t>(ctx->slot_bytes, kChunk + margin + 64),
-                       std::max<uint64_t>(ctx->slot_pkts, cap_pkts), false, out->detail != nullptr);
+  int rc = alloc_slots(ctx, std::max<uint64_t>(ctx->slot_bytes, F.chunk + F.margin + 64),
+                       std::max<uint64_t>(ctx->slot_pkts, F.cap_pkts), false, out->detail != nullptr);
   if (rc) return rc;
   SlotGuard guard{ctx};
   // Chunk k's work on slot k & 1: its bytes H2D, then (after chunk k-1's walk) its walk, its
@@ -1383,8 +1391,8 @@ static int decode_device_walk(gpd_ctx *ctx, const uint8_t *buf, uint64_t len, co
       drain_slot(s, out);
       s.busy = false;
     }
-    const uint64_t own = std::min<uint64_t>(kChunk, len - B);
-    const uint64_t T = std::min<uint64_t>(own + margin, len - B);
+    const uint64_t own = std::min<uint64_t>(F.chunk, len - B);
+    const uint64_t T = std::min<uint64_t>(own + F.margin, len - B);
     const bool last = B + own >= len;
     const uint8_t *src = buf + B;
     if (!ctx->is_registered(src, T)) {
@@ -1400,14 +1408,11 @@ static int decode_device_walk(gpd_ctx *ctx, const uint8_t *buf, uint64_t len, co
     } else {
       HIP_TRY(hipStreamWaitEvent(s.stream, ctx->ev_pw[(k - 1) & 1], 0));
     }
-    gpd::PwArgs A{};
+    Args A = F.state;
     A.d = s.d_data;
     A.T = (uint32_t)T;
     A.own_end = (uint32_t)own;
     A.nseg = (uint32_t)((own + gpd::kPwSeg - 1) / gpd::kPwSeg);
-    A.snaplen = I.snaplen;
-    A.be = I.big_endian != 0;
-    A.nano = I.nano != 0;
     A.last = last;
     A.ctl = dc;
     A.ctl_next = last ? nullptr : ctx->d_pw_ctl + ((k + 1) & 1);
@@ -1418,68 +1423,44 @@ static int decode_device_walk(gpd_ctx *ctx, const uint8_t *buf, uint64_t len, co
     A.base = s.d_pw + 4 * gpd::kPwMaxSeg;
     A.off = s.d_off;
     A.len = s.d_len;
-    hipError_t e = gpd::launch_pcap_walk(A, s.stream);
+    hipError_t e = F.walk(A, s.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(hc, dc, sizeof(gpd::PwCtl), hipMemcpyDeviceToHost, s.stream);
     if (e == hipSuccess) e = hipEventRecord(ctx->ev_pw[k & 1], s.stream);
-    if (e == hipSuccess) e = gpd::launch_pcap_fill(A, s.stream);
-    if (e != hipSuccess) return set_err(GPD_ERR_HIP, "gpd_decode_pcap: device walk: %s", hipGetErrorString(e));
-    gpd_batch b{s.d_data, T, s.d_off, s.d_len, cap_pkts};
+    if (e == hipSuccess) e = F.fill(A, s.stream);
+    if (e != hipSuccess) return set_err(GPD_ERR_HIP, "%s: device walk: %s", F.what, hipGetErrorString(e));
+    gpd_batch b{s.d_data, T, s.d_off, s.d_len, F.cap_pkts};
     gpd_result r{s.d_status, s.d_layers, s.d_nh, s.d_th, s.d_csum, nullptr, out->hdr_off ? s.d_hoff : nullptr,
                  nullptr, out->detail ? s.d_det : nullptr};
-    return launch(ctx, &b, &r, s.stream, false, &dc->n, std::max<uint64_t>(1, own / mean));
+    return launch(ctx, &b, &r, s.stream, false, &dc->n, std::max<uint64_t>(1, own / F.mean));
   };
   uint64_t B = pos & ~15ull;  // chunk base (16-byte aligned: the decoder's batch buffer)
-  uint64_t entry = pos - B;   // its first record header
+  uint64_t entry = pos - B;   // its first header
   uint64_t done = 0;
-  *resume = UINT64_MAX;
   rc = issue(0, B, entry);
   if (rc) return rc;
   for (int k = 0;; k++) {
     auto &s = ctx->slot[k & 1];
-    const uint64_t own = std::min<uint64_t>(kChunk, len - B);
+    const uint64_t own = std::min<uint64_t>(F.chunk, len - B);
     const bool last = B + own >= len;
-    // queue the next chunk now unless this one should end the call (its records, estimated
-    // from the mean record size, cover what is left)
-    const bool ahead = !last && done + own / mean < max_n;
+    // queue the next chunk now unless this one should end the call (its packets, estimated
+    // from the mean size, cover what is left)
+    const bool ahead = !last && done + own / F.mean < max_n;
     if (ahead && (rc = issue(k + 1, B + own, 0))) return rc;
     HIP_TRY(hipEventSynchronize(ctx->ev_pw[k & 1]));  // chunk k walked: its count
     const gpd::PwCtl c = ctx->h_pw_ctl[k & 1];
-    g_pw_counts[0]++;
-    g_pw_counts[6] += c.pad[0];
-    if (c.miss_at != 0xFFFFFFFFu) {
-      g_pw_miss[0] = B + c.miss_st;
-      g_pw_miss[1] = B + (uint64_t)c.miss_at * gpd::kPwSeg;
+    uint64_t take = 0;
+    if (!(c.status & 1u)) {  // (else the host walks from this chunk's entry: its decode saw 0 packets)
+      take = std::min<uint64_t>(c.n, max_n - done);
+      hipError_t e = results_d2h(ctx, s, out, done, take, s.stream);
+      if (e != hipSuccess) return set_err(GPD_ERR_HIP, "%s: D2H: %s", F.what, hipGetErrorString(e));
+      s.lo = done;
+      s.hi = done + take;
+      s.busy = take > 0;
+      done += take;
     }
-    if (c.status != 0) {
-      g_pw_counts[1]++;
-      for (int b = 0; b < 4; b++) g_pw_counts[2 + b] += (c.status >> (b + 1)) & 1u;  // the host walks from this chunk's entry (its decode saw 0 records)
-      *resume = B + entry;
-      break;
-    }
-    const uint64_t take = std::min<uint64_t>(c.n, max_n - done);
-    hipError_t e = results_d2h(ctx, s, out, done, take, s.stream);
-    if (e != hipSuccess) return set_err(GPD_ERR_HIP, "gpd_decode_pcap: D2H: %s", hipGetErrorString(e));
-    s.lo = done;
-    s.hi = done + take;
-    s.busy = take > 0;
-    done += take;
-    if (take < c.n) {  // the bound falls inside this chunk: the header of the record after it
-      HIP_TRY(hipMemcpyAsync(s.h_off, s.d_off + take, 4, hipMemcpyDeviceToHost, s.stream));
-      HIP_TRY(hipStreamSynchronize(s.stream));
-      if (next_pos) *next_pos = B + s.h_off[0] - GPD_PCAP_RECORD_BYTES;
-      if (stop) *stop = GPD_PCAP_STOP_LIMIT;
-      break;
-    }
-    if (done == max_n) {
-      if (next_pos) *next_pos = B + c.next;
-      if (stop) *stop = GPD_PCAP_STOP_LIMIT;
-      break;
-    }
-    if (last) {  // status 0 on the last chunk: the walk ended exactly at the capture's end
-      if (next_pos) *next_pos = len;
-      if (stop) *stop = GPD_PCAP_STOP_EOF;
-      break;
-    }
+    bool more = false;
+    if ((rc = on_chunk(SegChunk{c, B, entry, own, last, take, done, &s}, &more))) return rc;
+    if (!more) break;
     entry = c.next - own;
     B += own;
     if (!ahead && (rc = issue(k + 1, B, 0))) return rc;
@@ -1493,6 +1474,75 @@ static int decode_device_walk(gpd_ctx *ctx, const uint8_t *buf, uint64_t len, co
   }
   *handled = done;
   return GPD_OK;
+}
+
+extern "C" {
+
+// The pcap path with the record walk on the device (gpd_pcapwalk.hip): chunks of 64 MiB.
+// *handled records were decoded; *resume is the record header where the host walk must take
+// over (a chunk with status 1: a rejected record, a partial record at the end, a speculation
+// the walk missed), UINT64_MAX when the call is complete.
+static int decode_device_walk(gpd_ctx *ctx, const uint8_t *buf, uint64_t len, const gpd_pcap_info &I,
+                                   uint64_t pos, uint64_t max_n, const gpd_result *out, int nthreads,
+                                   uint64_t *handled, uint64_t *resume, uint64_t *next_pos, int *stop,
+                                   bool *ineligible) {
+  SegFormat<gpd::PwArgs> F{"gpd_decode_pcap"};
+  F.chunk = (uint64_t)gpd::kPwSeg * gpd::kPwMaxSeg;
+  F.margin = (16ull + I.snaplen + 31ull) & ~15ull;  // the longest record past a chunk
+  F.cap_pkts = F.chunk / GPD_PCAP_RECORD_BYTES;     // records a chunk can hold
+  *handled = 0;
+  *resume = pos;
+  // (records that long, or a capture whose first records cannot be indexed: the host walk,
+  // for the rest of the call — *ineligible)
+  *ineligible = true;
+  if (I.snaplen > (16u << 20)) return GPD_OK;
+  // the mean record size: the first records, walked here
+  {
+    uint64_t sp[64];
+    uint32_t sc[64];
+    gpd::PcapOut o;
+    o.pos64 = sp;
+    o.cap = sc;
+    gpd::PcapResult R;
+    if (gpd::pcap_index_flat(buf, len, I, pos, 64, 1, o, R) != GPD_OK || R.n == 0) return GPD_OK;
+    F.mean = std::max<uint64_t>(16, (R.next_pos - pos) / R.n);
+  }
+  *ineligible = false;
+  F.state.snaplen = I.snaplen;
+  F.state.be = I.big_endian != 0;
+  F.state.nano = I.nano != 0;
+  F.walk = gpd::launch_pcap_walk;
+  F.fill = gpd::launch_pcap_fill;
+  *resume = UINT64_MAX;
+  return seg_device_walk(ctx, buf, len, pos, max_n, out, nthreads, F, [&](const SegChunk &k, bool *more) -> int {
+    const gpd::PwCtl &c = k.c;
+    g_pw_counts[0]++;
+    g_pw_counts[6] += c.pad[0];
+    if (c.miss_at != 0xFFFFFFFFu) {
+      g_pw_miss[0] = k.B + c.miss_st;
+      g_pw_miss[1] = k.B + (uint64_t)c.miss_at * gpd::kPwSeg;
+    }
+    if (c.status != 0) {  // the host walks from this chunk's entry
+      g_pw_counts[1]++;
+      for (int b = 0; b < 4; b++) g_pw_counts[2 + b] += (c.status >> (b + 1)) & 1u;
+      *resume = k.B + k.entry;
+    } else if (k.take < c.n) {  // the bound falls inside this chunk: the header of the record after it
+      auto &s = *k.slot;
+      HIP_TRY(hipMemcpyAsync(s.h_off, s.d_off + k.take, 4, hipMemcpyDeviceToHost, s.stream));
+      HIP_TRY(hipStreamSynchronize(s.stream));
+      if (next_pos) *next_pos = k.B + s.h_off[0] - GPD_PCAP_RECORD_BYTES;
+      if (stop) *stop = GPD_PCAP_STOP_LIMIT;
+    } else if (k.done == max_n) {
+      if (next_pos) *next_pos = k.B + c.next;
+      if (stop) *stop = GPD_PCAP_STOP_LIMIT;
+    } else if (k.last) {  // status 0 on the last chunk: the walk ended exactly at the capture's end
+      if (next_pos) *next_pos = len;
+      if (stop) *stop = GPD_PCAP_STOP_EOF;
+    } else {
+      *more = true;
+    }
+    return GPD_OK;
+  }, handled);
 }
 
 // Records whose header starts in [pos, pos + span), as the ReadPacketData loop finds them, up to
@@ -1540,23 +1590,11 @@ int gpd_decode_pcap_at(gpd_ctx *ctx, const uint8_t *buf, uint64_t len, const gpd
   HIP_TRY(dscope_.set(ctx->device));
   bool dw = ctx->tune.device_walk != 0;
   uint64_t done = 0, at = pos;
-  auto shifted = [&](uint64_t d) {
-    gpd_result r = *out;
-    auto sh = [&](auto *p) { return p ? p + d : p; };
-    r.status = sh(out->status);
-    r.layers = sh(out->layers);
-    r.net_hash = sh(out->net_hash);
-    r.tp_hash = sh(out->tp_hash);
-    r.csum = sh(out->csum);
-    r.hdr_off = sh(out->hdr_off);
-    r.detail = sh(out->detail);
-    return r;
-  };
   for (;;) {
     if (dw) {
       uint64_t resume, handled = 0;
       bool ineligible = false;
-      const gpd_result r = shifted(done);
+      const gpd_result r = shifted(out, done);
       const int rc = decode_device_walk(ctx, buf, len, *info, at, max_n - done, &r, nthreads, &handled,
                                         &resume, next_pos, stop, &ineligible);
       done += handled;
@@ -1576,7 +1614,7 @@ int gpd_decode_pcap_at(gpd_ctx *ctx, const uint8_t *buf, uint64_t len, const gpd
       constexpr uint64_t kSpan = (uint64_t)gpd::kPwSeg * gpd::kPwMaxSeg;  // the device walk's chunk
       lim = std::min(lim, count_records(buf, len, *info, at, kSpan, lim) + 1u);
     }
-    const gpd_result r = shifted(done);
+    const gpd_result r = shifted(out, done);
     uint64_t k = 0, nxt = at;
     int st = GPD_PCAP_STOP_LIMIT;
     const int rc = decode_pcap_host_walk(ctx, buf, len, info, at, lim, &r, &k, &nxt, &st, nthreads);
@@ -1639,15 +1677,7 @@ int ng_decode_host_walk(gpd_ctx *ctx, gpd_pcapng_reader *r, uint64_t lim, const 
     if (rc != GPD_OK && rc != GPD_ERR_PCAPNG) return rc;
     if (n) {
       gpd_batch b{r->buf, r->len, off.data(), cap.data(), n};
-      gpd_result o = *out;
-      auto sh = [&](auto *p) { return p ? p + *k : p; };
-      o.status = sh(out->status);
-      o.layers = sh(out->layers);
-      o.net_hash = sh(out->net_hash);
-      o.tp_hash = sh(out->tp_hash);
-      o.csum = sh(out->csum);
-      o.hdr_off = sh(out->hdr_off);
-      o.detail = sh(out->detail);
+      const gpd_result o = shifted(out, *k);
       const int rd = gpd_decode_host(ctx, &b, &o);
       if (rd) return rd;
       *k += n;
@@ -1667,18 +1697,18 @@ int ng_device_walk(gpd_ctx *ctx, gpd_pcapng_reader *r, uint64_t max_n, const gpd
                    uint64_t *handled, NgHow *how, uint64_t *chunk_end) {
   const uint8_t *buf = r->buf;
   const uint64_t len = r->len;
-  const uint64_t chunk = r->opts.chunk_bytes ? r->opts.chunk_bytes : (uint64_t)gpd::kPwSeg * gpd::kPwMaxSeg;
-  constexpr uint64_t margin = 128u << 10;             // a block may run this far past its chunk
-  const uint64_t cap_pkts = (chunk + margin) / 16 + 64;  // a packet block takes 16 bytes or more
-  *handled = 0;
+  SegFormat<gpd::NgArgs> F{"gpd_decode_pcapng"};
+  F.chunk = r->opts.chunk_bytes ? r->opts.chunk_bytes : (uint64_t)gpd::kPwSeg * gpd::kPwMaxSeg;
+  F.margin = 128u << 10;                         // a block may run this far past its chunk
+  F.cap_pkts = (F.chunk + F.margin) / 16 + 64;   // a packet block takes 16 bytes or more
   const bool be = r->big_endian;
   auto rd = [&](uint64_t p) {
     uint32_t v;
     std::memcpy(&v, buf + p, 4);
     return be ? __builtin_bswap32(v) : v;
   };
-  // the mean block size (the decode's staging choices): the first blocks, read here
-  uint64_t mean = 96;
+  // the mean block size: the first blocks, read here
+  F.mean = 96;
   {
     uint64_t p = r->pos, nb = 0;
     while (nb < 64 && p + 12 <= len) {
@@ -1687,140 +1717,55 @@ int ng_device_walk(gpd_ctx *ctx, gpd_pcapng_reader *r, uint64_t max_n, const gpd
       p += total;
       nb++;
     }
-    if (nb) mean = std::max<uint64_t>(16, (p - r->pos) / nb);
+    if (nb) F.mean = std::max<uint64_t>(16, (p - r->pos) / nb);
   }
-  int rc = alloc_slots(ctx, std::max<uint64_t>(ctx->slot_bytes, chunk + margin + 64),
-                       std::max<uint64_t>(ctx->slot_pkts, cap_pkts), false, out->detail != nullptr);
-  if (rc) return rc;
-  SlotGuard guard{ctx};
   // the chunk state: what the walk needs of the reader's, constant until a state-changing block
-  gpd::NgArgs S{};
+  gpd::NgArgs &S = F.state;
   S.nif = (uint32_t)r->ifaces.size();
   for (uint32_t i = 0; i < S.nif; i++)
     if (r->ifaces[i].linktype == r->linktype) S.keep |= 1u << i;
   S.snaplen0 = S.nif ? r->ifaces[0].snaplen : 0;
   S.be = be;
   S.drop_is_error = r->opts.error_on_mismatching_linktype != 0;
-  auto issue = [&](int k, uint64_t B, uint64_t entry0, bool first) -> int {
-    auto &s = ctx->slot[k & 1];
-    if (s.busy) {
-      HIP_TRY(hipStreamSynchronize(s.stream));
-      drain_slot(s, out);
-      s.busy = false;
-    }
-    const uint64_t own = std::min<uint64_t>(chunk, len - B);
-    const uint64_t T = std::min<uint64_t>(own + margin, len - B);
-    const bool last = B + own >= len;
-    const uint8_t *src = buf + B;
-    if (!ctx->is_registered(src, T)) {
-      HIP_TRY(hipStreamSynchronize(s.stream));  // (its staging buffer may still be read)
-      par_memcpy(s.h_data, src, T, nthreads);
-      src = s.h_data;
-    }
-    gpd::PwCtl *dc = ctx->d_pw_ctl + (k & 1), *hc = ctx->h_pw_ctl + (k & 1);
-    HIP_TRY(hipMemcpyAsync(s.d_data, src, T, hipMemcpyHostToDevice, s.stream));
-    if (first) {
-      hc->entry = (uint32_t)entry0;
-      HIP_TRY(hipMemcpyAsync(&dc->entry, &hc->entry, 4, hipMemcpyHostToDevice, s.stream));
-    } else {
-      HIP_TRY(hipStreamWaitEvent(s.stream, ctx->ev_pw[(k - 1) & 1], 0));
-    }
-    gpd::NgArgs A = S;
-    A.d = s.d_data;
-    A.T = (uint32_t)T;
-    A.own_end = (uint32_t)own;
-    A.nseg = (uint32_t)((own + gpd::kPwSeg - 1) / gpd::kPwSeg);
-    A.last = last;
-    A.ctl = dc;
-    A.ctl_next = last ? nullptr : ctx->d_pw_ctl + ((k + 1) & 1);
-    A.st = s.d_pw;
-    A.ex = s.d_pw + gpd::kPwMaxSeg;
-    A.ct = s.d_pw + 2 * gpd::kPwMaxSeg;
-    A.bad = s.d_pw + 3 * gpd::kPwMaxSeg;
-    A.base = s.d_pw + 4 * gpd::kPwMaxSeg;
-    A.off = s.d_off;
-    A.len = s.d_len;
-    hipError_t e = gpd::launch_ng_walk(A, s.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hc, dc, sizeof(gpd::PwCtl), hipMemcpyDeviceToHost, s.stream);
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev_pw[k & 1], s.stream);
-    if (e == hipSuccess) e = gpd::launch_ng_fill(A, s.stream);
-    if (e != hipSuccess) return set_err(GPD_ERR_HIP, "gpd_decode_pcapng: device walk: %s", hipGetErrorString(e));
-    gpd_batch b{s.d_data, T, s.d_off, s.d_len, cap_pkts};
-    gpd_result res{s.d_status, s.d_layers, s.d_nh, s.d_th, s.d_csum, nullptr, out->hdr_off ? s.d_hoff : nullptr,
-                   nullptr, out->detail ? s.d_det : nullptr};
-    return launch(ctx, &b, &res, s.stream, false, &dc->n, std::max<uint64_t>(1, own / mean));
-  };
-  uint64_t B = r->pos & ~15ull;  // chunk base (16-byte aligned: the decoder's batch buffer)
-  uint64_t entry = r->pos - B;   // its first block header
-  uint64_t done = 0;
+  F.walk = gpd::launch_ng_walk;
+  F.fill = gpd::launch_ng_fill;
   *how = kNgLimit;
-  rc = issue(0, B, entry, true);
-  if (rc) return rc;
-  for (int k = 0;; k++) {
-    auto &s = ctx->slot[k & 1];
-    const uint64_t own = std::min<uint64_t>(chunk, len - B);
-    const bool last = B + own >= len;
-    // queue the next chunk now unless this one should end the call (its packets, estimated
-    // from the mean block size, cover what is left)
-    const bool ahead = !last && done + own / mean < max_n;
-    if (ahead && (rc = issue(k + 1, B + own, 0, false))) return rc;
-    HIP_TRY(hipEventSynchronize(ctx->ev_pw[k & 1]));  // chunk k walked: its count
-    const gpd::PwCtl c = ctx->h_pw_ctl[k & 1];
+  return seg_device_walk(ctx, buf, len, r->pos, max_n, out, nthreads, F, [&](const SegChunk &k, bool *more) -> int {
+    const gpd::PwCtl &c = k.c;
     g_ng_counts[0]++;
     g_ng_counts[7] += c.pad[0];
-    if (c.status & 1u) {  // the host walks this chunk from its entry (its decode saw 0 packets)
+    if (c.status & 1u) {  // the host walks this chunk from its entry
       g_ng_counts[1]++;
       g_ng_counts[3] += (c.status >> 1) & 1u;
       g_ng_counts[5] += (c.status >> 3) & 1u;
       g_ng_counts[6] += (c.status >> 4) & 1u;
-      r->pos = B + entry;
-      *chunk_end = B + own;
+      r->pos = k.B + k.entry;
+      *chunk_end = k.B + k.own;
       *how = kNgHostChunk;
-      break;
+      return GPD_OK;
     }
-    const uint64_t take = std::min<uint64_t>(c.n, max_n - done);
-    hipError_t e = results_d2h(ctx, s, out, done, take, s.stream);
-    if (e != hipSuccess) return set_err(GPD_ERR_HIP, "gpd_decode_pcapng: D2H: %s", hipGetErrorString(e));
-    s.lo = done;
-    s.hi = done + take;
-    s.busy = take > 0;
-    done += take;
-    if (take < c.n) {  // the bound falls inside this chunk: the reader walks to it from the entry
-      r->pos = B + entry;
+    if (k.take < c.n) {  // the bound falls inside this chunk: the reader walks to it from the entry
+      r->pos = k.B + k.entry;
       gpd::NgPacket p;
-      for (uint64_t i = 0; i < take; i++)
+      for (uint64_t i = 0; i < k.take; i++)
         if (r->next_packet(&p)) return set_err(GPD_ERR_INVALID, "gpd_decode_pcapng: host and device walks disagree");
       *how = kNgLimit;
-      break;
+      return GPD_OK;
     }
-    r->pos = B + c.next;
-    if (done == max_n) {
+    r->pos = k.B + c.next;
+    if (k.done == max_n) {
       *how = kNgLimit;
-      break;
-    }
-    if (c.status & (gpd::kNgTailState | gpd::kNgTailBlock)) {
+    } else if (c.status & (gpd::kNgTailState | gpd::kNgTailBlock)) {
       g_ng_counts[2]++;
       g_ng_counts[4] += (c.status & gpd::kNgTailBlock) != 0;
       *how = (c.status & gpd::kNgTailState) ? kNgState : kNgBlock;
-      break;
-    }
-    if (last) {  // status 0 on the last chunk: the walk ended exactly at the capture's end
+    } else if (k.last) {  // status 0 on the last chunk: the walk ended exactly at the capture's end
       *how = kNgEof;
-      break;
+    } else {
+      *more = true;
     }
-    entry = c.next - own;
-    B += own;
-    if (!ahead && (rc = issue(k + 1, B, 0, false))) return rc;
-  }
-  for (auto &s : ctx->slot) {  // (a chunk queued ahead and not needed is waited for and dropped)
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    if (s.busy) {
-      drain_slot(s, out);
-      s.busy = false;
-    }
-  }
-  *handled = done;
-  return GPD_OK;
+    return GPD_OK;
+  }, handled);
 }
 
 }  // namespace
@@ -1843,18 +1788,6 @@ int gpd_decode_pcapng(gpd_ctx *ctx, gpd_pcapng_reader *r, uint64_t max_n, const 
   gpd::DeviceScope dscope_;
   HIP_TRY(dscope_.set(ctx->device));
   uint64_t done = 0;
-  auto shifted = [&](uint64_t d) {
-    gpd_result o = *out;
-    auto sh = [&](auto *p) { return p ? p + d : p; };
-    o.status = sh(out->status);
-    o.layers = sh(out->layers);
-    o.net_hash = sh(out->net_hash);
-    o.tp_hash = sh(out->tp_hash);
-    o.csum = sh(out->csum);
-    o.hdr_off = sh(out->hdr_off);
-    o.detail = sh(out->detail);
-    return o;
-  };
   auto finish = [&](int st) {
     *n_out = done;
     if (stop) *stop = st;
@@ -1871,7 +1804,7 @@ int gpd_decode_pcapng(gpd_ctx *ctx, gpd_pcapng_reader *r, uint64_t max_n, const 
     if (dw && r->ifaces.size() <= gpd::kNgMaxIfaces && r->pos < r->len) {
       uint64_t handled = 0, chunk_end = 0;
       NgHow how = kNgLimit;
-      const gpd_result o = shifted(done);
+      const gpd_result o = shifted(out, done);
       const int rc = ng_device_walk(ctx, r, max_n - done, &o, nthreads, &handled, &how, &chunk_end);
       done += handled;
       *n_out = done;
@@ -1893,7 +1826,7 @@ int gpd_decode_pcapng(gpd_ctx *ctx, gpd_pcapng_reader *r, uint64_t max_n, const 
     // The host walk: all of the call without the device walk; else the one packet behind a
     // block the device does not vouch for, or the chunk it gave up, and then the device again.
     while (lim && !r->stop && r->pos < until) {
-      const gpd_result o = shifted(done);
+      const gpd_result o = shifted(out, done);
       uint64_t k = 0;
       int st = GPD_PCAPNG_STOP_LIMIT;
       const int rc = ng_decode_host_walk(ctx, r, std::min<uint64_t>(lim, until == UINT64_MAX ? lim : 256), &o, &k, &st);

@@ -92,6 +92,12 @@ def test_device_walk_stops_where_the_reader_does():
     bad[p0 + 8:p0 + 12] = np.frombuffer(struct.pack("<I", 300000), np.uint8)
     n, err, ph = _both(bad)
     assert n == 100000 and err.startswith("capture length exceeds snap length")
+    # ... and the device walk says why: one chunk handed over, for a rejected record
+    from gopacket_amd._lib import lib
+    _parser(1).DecodePcap(bad, nthreads=8)
+    wc = np.zeros(7, np.uint32)
+    lib.gpd_decode_pcap_last_walk_counts(wc.ctypes.data)
+    assert wc[1] == 1 and wc[3] == 1, wc
     # caplen > original length
     bad2 = cap.copy()
     bad2[p0 + 12:p0 + 16] = np.frombuffer(struct.pack("<I", 1), np.uint8)
