@@ -28,11 +28,13 @@ DIAG_LIB = os.path.join(PKG, "libgpd_diag.so")
 ORACLE_LIB = os.path.join(ROOT, "oracle", "libgpd_oracle.so")
 
 SOURCES = [os.path.join(CSRC, "gpd_kernels.hip"), os.path.join(CSRC, "gpd_runtime.cpp"),
+           os.path.join(CSRC, "gpd_staging.cpp"), os.path.join(CSRC, "gpd_capture.cpp"),
            os.path.join(CSRC, "gpd_pcap.cpp"), os.path.join(CSRC, "gpd_flow.hip"),
            os.path.join(CSRC, "gpd_pcapwalk.hip"), os.path.join(CSRC, "gpd_tpv3walk.hip"),
            os.path.join(CSRC, "gpd_afpacket.cpp"), os.path.join(CSRC, "gpd_pcapng.cpp"),
            os.path.join(CSRC, "gpd_ngwalk.hip")]
-HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_segwalk.h"),
+HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h"),
+           os.path.join(CSRC, "gpd_segwalk.h"),
            os.path.join(ROOT, "include", "gpd.h"),
            os.path.join(ROOT, "include", "gpd_pcap.h"), os.path.join(ROOT, "include", "gpd_flow.h"),
            os.path.join(ROOT, "include", "gpd_afpacket.h"), os.path.join(ROOT, "include", "gpd_defrag.h"),

@@ -26,7 +26,7 @@
 #include <thread>
 #include <vector>
 
-#include "gpd_internal.h"
+#include "gpd_ctx.h"
 #include "../../include/gpd_afpacket.h"
 
 namespace {
@@ -38,6 +38,7 @@ struct BlockPlan {
   uint32_t ring_block;  // index in the ring
   uint32_t emit;        // packets the read loop returns from it
   uint64_t out;         // index of its first packet in the output
+  uint64_t entry;       // its first emitted packet header, relative to the block (the device walk's)
 };
 
 // Packets ZeroCopyReadPacketData returns from one user-owned block (see the file comment):
@@ -121,7 +122,10 @@ int plan_walk(const gpd_tpv3_ring *R, uint32_t first, uint32_t max_blocks, uint6
                               (unsigned long long)max_n, k, e);
       break;
     }
-    plan.push_back(BlockPlan{k, e, n});
+    uint64_t entry = e ? bh.offset_to_first_pkt : 0;
+    if (e && p0->tp_len == 0)  // afpacket.go:313-316: the retry's next() (header.go:181-195)
+      entry += p0->tp_next_offset != 0 ? (uint64_t)p0->tp_next_offset : tp_align((uint64_t)p0->tp_snaplen + p0->tp_mac);
+    plan.push_back(BlockPlan{k, e, n, entry});
     n += e;
   }
   return GPD_OK;
@@ -132,7 +136,7 @@ thread_local int g_last_path = 0;  // gpd_decode_tpv3_last_path
 int run_walk(const gpd_tpv3_ring *R, const std::vector<BlockPlan> &plan, const gpd_tpv3_pkts &pk,
              int nthreads, uint32_t *off32 = nullptr) {
   // nthreads <= 0: the machine's cores, at most 16 (blocks are few and cheap to walk)
-  int T = nthreads > 0 ? nthreads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  int T = gpd::default_threads(nthreads);
   T = (int)std::min<size_t>((size_t)T, plan.size());
   if (plan.size() < 8) T = 1;  // a thread per block costs more than walking a few blocks
   if (T <= 1) {
@@ -151,6 +155,200 @@ int run_walk(const gpd_tpv3_ring *R, const std::vector<BlockPlan> &plan, const g
   for (auto &x : th) x.join();
   for (int r : rc)
     if (r) return gpd::set_error(r, "tpv3: corrupt block (see the walk)");
+  return GPD_OK;
+}
+
+// ---- TPACKET_V3 ring: the blocks H2D in groups, walked and decoded on the device ----
+constexpr uint64_t kTwPkts = 1u << 19;       // packets per group
+constexpr uint64_t kTwMaxBlocks = 16384;     // blocks per group
+constexpr uint64_t kTwTab = kTwMaxBlocks * sizeof(gpd::TwBlock), kTwSt = kTwMaxBlocks * 4;
+// A group's per-packet arrays packed into one region, so one D2H brings them back: decode
+// results, caplen (the walk's, the decode's input), then the capture info, each array
+// 256-byte aligned.  The region is laid out for the group's packet count m.
+// The detail records come last: they travel (in a copy of their own) only when asked for.
+enum TwArr { kLayers, kNh, kTh, kStatus, kCsum, kHoff, kCap, kCiOff, kCiTs, kCiWire, kCiIfx, kCiVlan, kCiTci, kDet,
+             kTwN };
+// the result array (gpd_ctx.h) each region array holds (-1: capture info, with its width here)
+constexpr int kTwRes[kTwN] = {gpd::kResLayers, gpd::kResNetHash, gpd::kResTpHash, gpd::kResStatus, gpd::kResCsum,
+                              gpd::kResHdrOff, -1, -1, -1, -1, -1, -1, -1, gpd::kResDetail};
+constexpr uint64_t kTwCiW[kTwN] = {0, 0, 0, 0, 0, 0, 4, 8, 8, 4, 4, 4, 4, 0};
+constexpr uint64_t tw_w(int q) { return kTwRes[q] >= 0 ? gpd::kResW.w[kTwRes[q]] : kTwCiW[q]; }
+struct TwLay {
+  uint64_t off[kTwN + 1];  // off[kCiOff]: the end of the results; off[kDet]: of the capture info
+  explicit TwLay(uint64_t m) {
+    uint64_t o = 0;
+    for (int a = 0; a < kTwN; a++) {
+      off[a] = o;
+      o += (tw_w(a) * m + 255) & ~255ull;
+    }
+    off[kTwN] = o;
+  }
+};
+const uint64_t kTwRegion = TwLay(kTwPkts).off[kTwN];
+// a slot's d_tw: the group's block table, its status words, its region.  Its h_tw: two of
+// each (a slot holds groups k and k + 2 at once: k + 2 is queued before the host copies k out).
+constexpr uint64_t kTwDevSt = kTwTab;
+inline uint64_t tw_dreg() { return kTwTab + kTwSt; }
+inline uint64_t tw_htab(uint32_t set) { return set * kTwTab; }
+inline uint64_t tw_hst(uint32_t set) { return 2 * kTwTab + set * kTwSt; }
+inline uint64_t tw_hreg(uint32_t set) { return 2 * kTwTab + 2 * kTwSt + set * kTwRegion; }
+
+// gpd_decode_tpv3 with the block walk on the device: the planned blocks travel to HBM in groups
+// of consecutive ring blocks, are walked there (gpd_tpv3walk.hip) and decoded, and results and
+// capture info come back.  *fallback: the device path does not apply (tuning, geometry, a
+// block the walk rejects, a tagged frame with add_vlan) and the caller runs the host path for
+// the whole call (nothing returned so far counts).
+int decode_tpv3_device(gpd_ctx *ctx, const gpd_tpv3_ring &R, const std::vector<BlockPlan> &plan, bool add_vlan,
+                       const gpd_tpv3_pkts *pk, const gpd_result *out, int nthreads, bool *fallback) {
+  *fallback = true;
+  const uint64_t B = R.block_size;
+  if (ctx->tune.device_walk == 0 || out->ext || out->records || (B & 15u) || B > gpd::kTwGroup || plan.empty())
+    return GPD_OK;
+  for (const auto &p : plan)
+    if (p.emit > kTwPkts || (p.emit && (p.entry + 48 > B || (p.entry & 15u)))) return GPD_OK;
+  nthreads = gpd::default_threads(nthreads);
+  gpd::DeviceScope dscope_;
+  HIP_TRY(dscope_.set(ctx->device));
+  int rc = gpd::alloc_slots(ctx, std::max<uint64_t>(ctx->slot_bytes, gpd::kTwGroup),
+                       std::max<uint64_t>(ctx->slot_pkts, kTwPkts), false, false);
+  if (rc) return rc;
+  for (auto &s : ctx->slot) {  // (tens of MiB that most contexts never use: on first use)
+    if (!s.d_tw) HIP_TRY(hipMalloc(&s.d_tw, tw_dreg() + kTwRegion));
+    if (!s.h_tw) HIP_TRY(hipHostMalloc(&s.h_tw, tw_hreg(2), hipHostMallocDefault));
+  }
+  gpd::SlotGuard guard{ctx};
+  const bool ci = pk != nullptr;
+  struct Group {
+    uint64_t lo = 0, m = 0;
+    uint32_t nb = 0, set = 0;
+    bool direct = false;
+  };
+  std::vector<Group> grp;
+  // the caller's array for each region array (NULL: not asked for)
+  const gpd::ResPtrs asked = gpd::res_ptrs(*out);
+  void *dst[kTwN] = {};
+  for (int q = 0; q < kTwN; q++)
+    if (kTwRes[q] >= 0) dst[q] = asked.p[kTwRes[q]];
+  if (ci) {
+    dst[kCap] = pk->caplen, dst[kCiOff] = pk->offset, dst[kCiTs] = pk->ts_ns, dst[kCiWire] = pk->wire_len;
+    dst[kCiIfx] = pk->ifindex, dst[kCiVlan] = pk->vlan, dst[kCiTci] = pk->vlan_tci;
+  }
+  // group k done: every block walked as the host would, then its results copied out
+  auto complete = [&](size_t k) -> int {
+    HIP_TRY(hipEventSynchronize(ctx->ev_tw[k & 3]));
+    const Group &G = grp[k];
+    const auto &s = ctx->slot[k & 1];
+    const uint32_t *st = reinterpret_cast<const uint32_t *>(s.h_tw + tw_hst(G.set));
+    uint32_t any = 0;
+    for (uint32_t b = 0; b < G.nb; b++) any |= st[b];
+    if ((any & 1u) || (add_vlan && (any & 2u))) return 1;
+    if (!G.direct && G.m) {
+      const TwLay L(G.m);
+      const uint8_t *reg = s.h_tw + tw_hreg(G.set);
+      gpd::par_for(G.m, 1u << 15, [&](uint64_t a, uint64_t b) {
+        for (int q = 0; q < kTwN; q++)
+          if (dst[q])
+            std::memcpy(static_cast<uint8_t *>(dst[q]) + (G.lo + a) * tw_w(q), reg + L.off[q] + a * tw_w(q),
+                        (b - a) * tw_w(q));
+      });
+    }
+    return GPD_OK;
+  };
+  // Group k goes to slot k & 1 and host buffers (k >> 1) & 1.  Its bytes go on the copy
+  // stream (all groups in order), its walk and decode on the slot's stream, its D2H on the
+  // slot's second stream, so no transfer queues behind a kernel.  Group k is queued before the
+  // host waits for group k - 2 and copies it out, so no stream waits for the host.
+  size_t a = 0;
+  while (a < plan.size()) {
+    // the group: consecutive ring blocks (no wrap) within the byte, block and packet bounds
+    size_t b = a + 1;
+    uint64_t m = plan[a].emit;
+    while (b < plan.size() && plan[b].ring_block == plan[b - 1].ring_block + 1 && (b - a + 1) * B <= gpd::kTwGroup &&
+           b - a < kTwMaxBlocks && m + plan[b].emit <= kTwPkts)
+      m += plan[b++].emit;
+    const size_t k = grp.size();
+    auto &s = ctx->slot[k & 1];
+    Group G;
+    G.lo = plan[a].out;
+    G.m = m;
+    G.nb = (uint32_t)(b - a);
+    G.set = (uint32_t)((k >> 1) & 1);
+    const uint64_t bytes = (uint64_t)G.nb * B;
+    const TwLay L(std::max<uint64_t>(m, 1));
+    auto *tb = reinterpret_cast<gpd::TwBlock *>(s.h_tw + tw_htab(G.set));  // (group k - 4's: done)
+    for (uint32_t q = 0; q < G.nb; q++)
+      tb[q] = gpd::TwBlock{(uint32_t)plan[a + q].entry, plan[a + q].emit, (uint32_t)(plan[a + q].out - G.lo), 0};
+    s.busy = true;  // (work in flight from here: an error exit waits for it)
+    // the bytes on the copy stream, right behind the previous group's (the link stays busy
+    // while groups are walked), once group k - 2's decode has read the slot's buffer
+    if (k >= 2) HIP_TRY(hipStreamWaitEvent(ctx->tw_in, ctx->ev_twdec[(k - 2) & 3], 0));
+    HIP_TRY(gpd::stage_h2d(ctx, s, R.base + (uint64_t)plan[a].ring_block * B, bytes, nthreads, ctx->tw_in, [&] {
+      return k >= 2 ? hipEventSynchronize(ctx->ev_twin[k & 1]) : hipSuccess;  // group k - 2's bytes are in HBM
+    }));
+    HIP_TRY(hipEventRecord(ctx->ev_twin[k & 1], ctx->tw_in));
+    HIP_TRY(hipStreamWaitEvent(s.stream, ctx->ev_twin[k & 1], 0));
+    HIP_TRY(hipMemcpyAsync(s.d_tw, tb, G.nb * sizeof(gpd::TwBlock), hipMemcpyHostToDevice, s.stream));
+    // the region and status words are group k - 2's until its D2H is done
+    if (k >= 2) HIP_TRY(hipStreamWaitEvent(s.stream, ctx->ev_tw[(k - 2) & 3], 0));
+    uint8_t *dr = s.d_tw + tw_dreg();
+    auto dev = [&](int q) { return dr + L.off[q]; };
+    gpd::TwArgs A{};
+    A.d = s.d_data;
+    A.block_size = (uint32_t)B;
+    A.nblk = G.nb;
+    A.ring_off0 = (uint64_t)plan[a].ring_block * B;
+    A.blk = reinterpret_cast<const gpd::TwBlock *>(s.d_tw);
+    A.st = reinterpret_cast<uint32_t *>(s.d_tw + kTwDevSt);
+    A.off = s.d_off;
+    A.len = reinterpret_cast<uint32_t *>(dev(kCap));
+    if (ci) {
+      A.ci_off = reinterpret_cast<uint64_t *>(dev(kCiOff));
+      A.ci_ts = reinterpret_cast<uint64_t *>(dev(kCiTs));
+      A.ci_wire = reinterpret_cast<uint32_t *>(dev(kCiWire));
+      A.ci_ifx = reinterpret_cast<int32_t *>(dev(kCiIfx));
+      A.ci_vlan = reinterpret_cast<int32_t *>(dev(kCiVlan));
+      A.ci_tci = reinterpret_cast<uint32_t *>(dev(kCiTci));
+    }
+    hipError_t e = gpd::launch_tpv3_walk(A, s.stream);
+    if (e != hipSuccess) return gpd::set_error(GPD_ERR_HIP, "gpd_decode_tpv3: device walk: %s", hipGetErrorString(e));
+    if (m) {
+      gpd_batch bt{s.d_data, bytes, s.d_off, A.len, m};
+      gpd::ResPtrs rp;
+      for (int q = 0; q < kTwN; q++)
+        if (kTwRes[q] >= 0 && gpd::res_wanted(asked, kTwRes[q])) rp.p[kTwRes[q]] = dev(q);
+      const gpd_result r = gpd::res_struct(rp);
+      if ((rc = gpd::decode_launch(ctx, &bt, &r, s.stream, false))) return rc;
+    }
+    HIP_TRY(hipEventRecord(ctx->ev_twdec[k & 3], s.stream));
+    HIP_TRY(hipStreamWaitEvent(s.stream_out, ctx->ev_twdec[k & 3], 0));
+    HIP_TRY(hipMemcpyAsync(s.h_tw + tw_hst(G.set), A.st, G.nb * 4, hipMemcpyDeviceToHost, s.stream_out));
+    if (m) {
+      G.direct = true;
+      for (int q = 0; q < kTwN; q++)
+        G.direct = G.direct && (!dst[q] || ctx->is_registered(static_cast<uint8_t *>(dst[q]) + G.lo * tw_w(q),
+                                                               m * tw_w(q)));
+      if (G.direct) {
+        for (int q = 0; q < kTwN; q++)
+          if (dst[q])
+            HIP_TRY(hipMemcpyAsync(static_cast<uint8_t *>(dst[q]) + G.lo * tw_w(q), dev(q), m * tw_w(q),
+                                   hipMemcpyDeviceToHost, s.stream_out));
+      } else {
+        HIP_TRY(hipMemcpyAsync(s.h_tw + tw_hreg(G.set), dr, L.off[ci ? kDet : kCiOff], hipMemcpyDeviceToHost,
+                               s.stream_out));
+        if (out->detail)
+          HIP_TRY(hipMemcpyAsync(s.h_tw + tw_hreg(G.set) + L.off[kDet], dr + L.off[kDet], m * tw_w(kDet),
+                                 hipMemcpyDeviceToHost, s.stream_out));
+      }
+    }
+    HIP_TRY(hipEventRecord(ctx->ev_tw[k & 3], s.stream_out));
+    grp.push_back(G);
+    if (k >= 2 && (rc = complete(k - 2))) return rc == 1 ? GPD_OK : rc;  // (the guard waits)
+    a = b;
+  }
+  for (size_t k = grp.size() >= 2 ? grp.size() - 2 : 0; k < grp.size(); k++)
+    if ((rc = complete(k))) return rc == 1 ? GPD_OK : rc;
+  for (auto &s : ctx->slot) s.busy = false;
+  *fallback = false;
   return GPD_OK;
 }
 
@@ -203,34 +401,17 @@ int gpd_decode_tpv3(gpd_ctx *ctx, const gpd_tpv3_ring *ring, uint32_t first_bloc
   uint64_t n = 0;
   int rc = plan_walk(ring, first_block, max_blocks, max_n, plan, n);
   if (rc || plan.empty()) return rc;
-  {
-    // The walk on the device (gpd_tpv3walk.hip): each block's first emitted packet from its
-    // descriptor here, every other step there.  It declines (tuning, geometry, a walk leaving
-    // its block, a tag to insert) before anything it returned counts; the host path follows.
-    std::vector<gpd::TwPlan> tp(plan.size());
-    for (size_t j = 0; j < plan.size(); j++) {
-      const BlockPlan &bp = plan[j];
-      uint64_t entry = 0;
-      if (bp.emit) {
-        const uint8_t *blk = ring->base + (uint64_t)bp.ring_block * ring->block_size;
-        const tpacket_hdr_v1 &bh = reinterpret_cast<const tpacket_block_desc *>(blk)->hdr.bh1;
-        entry = bh.offset_to_first_pkt;
-        const auto *p0 = reinterpret_cast<const tpacket3_hdr *>(blk + entry);
-        if (p0->tp_len == 0)  // afpacket.go:313-316: the retry's next() (header.go:181-195)
-          entry += p0->tp_next_offset != 0 ? (uint64_t)p0->tp_next_offset
-                                           : tp_align((uint64_t)p0->tp_snaplen + p0->tp_mac);
-      }
-      tp[j] = gpd::TwPlan{bp.ring_block, bp.emit, bp.out, entry};
-    }
-    bool fallback = true;
-    rc = gpd::decode_tpv3_device(ctx, *ring, tp, n, add_vlan_header != 0, pk_out, out, nthreads, &fallback);
-    if (rc) return rc;
-    if (!fallback) {
-      g_last_path = 1;
-      *n_out = n;
-      *blocks_out = (uint32_t)plan.size();
-      return GPD_OK;
-    }
+  // The walk on the device (gpd_tpv3walk.hip): each block's first emitted packet from its
+  // descriptor here, every other step there.  It declines (tuning, geometry, a walk leaving
+  // its block, a tag to insert) before anything it returned counts; the host path follows.
+  bool fallback = true;
+  rc = decode_tpv3_device(ctx, *ring, plan, add_vlan_header != 0, pk_out, out, nthreads, &fallback);
+  if (rc) return rc;
+  if (!fallback) {
+    g_last_path = 1;
+    *n_out = n;
+    *blocks_out = (uint32_t)plan.size();
+    return GPD_OK;
   }
   // the walk writes straight into the caller's arrays where it has them
   std::vector<uint64_t> off_own;
@@ -304,23 +485,19 @@ int gpd_decode_tpv3(gpd_ctx *ctx, const gpd_tpv3_ring *ring, uint32_t first_bloc
   gpd::DeviceScope dscope_;
   if (dscope_.set(gpd::ctx_device(ctx)) != hipSuccess)
     return gpd::set_error(GPD_ERR_HIP, "gpd_decode_tpv3: hipSetDevice");
-  // context scratch slots 0-8 (kept across calls: a ring is walked again and again)
+  // context scratch slots 0-10 (kept across calls: a ring is walked again and again)
   auto *d_data = static_cast<uint8_t *>(gpd::ctx_scratch(ctx, 0, ((data_len + 15) & ~15ull) + 64));
   uint32_t *d_off = static_cast<uint32_t *>(gpd::ctx_scratch(ctx, 1, n * 4));
   uint32_t *d_cap = static_cast<uint32_t *>(gpd::ctx_scratch(ctx, 2, n * 4));
-  uint32_t *d_st = static_cast<uint32_t *>(gpd::ctx_scratch(ctx, 3, n * 4));
-  uint32_t *d_cs = static_cast<uint32_t *>(gpd::ctx_scratch(ctx, 4, n * 4));
-  uint32_t *d_ho = static_cast<uint32_t *>(gpd::ctx_scratch(ctx, 5, n * 4));
-  uint64_t *d_ly = static_cast<uint64_t *>(gpd::ctx_scratch(ctx, 6, n * 8));
-  uint64_t *d_nh = static_cast<uint64_t *>(gpd::ctx_scratch(ctx, 7, n * 8));
-  uint64_t *d_th = static_cast<uint64_t *>(gpd::ctx_scratch(ctx, 8, n * 8));
-  gpd_detail *d_dt = out->detail ? static_cast<gpd_detail *>(gpd::ctx_scratch(ctx, 9, n * sizeof(gpd_detail)))
-                                 : nullptr;
-  hipError_t e = hipSuccess;
-  for (void *p : {(void *)d_data, (void *)d_off, (void *)d_cap, (void *)d_st, (void *)d_cs,
-                  (void *)d_ho, (void *)d_ly, (void *)d_nh, (void *)d_th})
-    if (!p) e = hipErrorOutOfMemory;
-  if (out->detail && !d_dt) e = hipErrorOutOfMemory;
+  // the result arrays in scratch slots 3.. (one per array of the list; no ext here, detail when asked for)
+  const gpd::ResPtrs asked = gpd::res_ptrs(*out);
+  gpd::ResPtrs dres;
+  hipError_t e = d_data && d_off && d_cap ? hipSuccess : hipErrorOutOfMemory;
+  for (int a = 0; a < gpd::kNumRes; a++) {
+    if (a == gpd::kResExt || (a == gpd::kResDetail && !asked.p[a])) continue;
+    dres.p[a] = static_cast<uint8_t *>(gpd::ctx_scratch(ctx, 3 + a, n * gpd::kResW.w[a]));
+    if (!dres.p[a]) e = hipErrorOutOfMemory;
+  }
   // the walked blocks, ring order from first_block (one copy per contiguous run)
   for (uint64_t j = 0; j < nb && e == hipSuccess;) {
     uint64_t k = j + 1;
@@ -335,19 +512,13 @@ int gpd_decode_tpv3(gpd_ctx *ctx, const gpd_tpv3_ring *ring, uint32_t first_bloc
   if (e == hipSuccess) e = hipMemcpy(d_cap, dcap.data(), n * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     gpd_batch b{d_data, data_len, d_off, d_cap, n};
-    gpd_result r{d_st, d_ly, d_nh, d_th, d_cs, nullptr, d_ho, nullptr, d_dt};
+    const gpd_result r = gpd::res_struct(dres);
     rc = gpd_decode(ctx, &b, &r, nullptr);
     if (rc == GPD_OK) e = hipDeviceSynchronize();
   }
   if (e == hipSuccess && rc == GPD_OK) {
-    e = hipMemcpy(out->status, d_st, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out->layers, d_ly, n * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out->net_hash) e = hipMemcpy(out->net_hash, d_nh, n * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out->tp_hash) e = hipMemcpy(out->tp_hash, d_th, n * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out->csum) e = hipMemcpy(out->csum, d_cs, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out->hdr_off) e = hipMemcpy(out->hdr_off, d_ho, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out->detail)
-      e = hipMemcpy(out->detail, d_dt, n * sizeof(gpd_detail), hipMemcpyDeviceToHost);
+    for (int a = 0; a < gpd::kNumRes && e == hipSuccess; a++)
+      if (asked.p[a]) e = hipMemcpy(asked.p[a], dres.p[a], n * gpd::kResW.w[a], hipMemcpyDeviceToHost);
   }
   if (rc) return rc;
   if (e != hipSuccess) return gpd::set_error(GPD_ERR_HIP, "gpd_decode_tpv3: %s", hipGetErrorString(e));

@@ -1,4 +1,5 @@
 // gpd_internal.h — shared between the HIP kernels and the host runtime (not public ABI).
+// The context itself (struct gpd_ctx) is host-only: gpd_ctx.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -260,24 +261,7 @@ int pcap_locate(const uint8_t *buf, uint64_t len, const gpd_pcap_info &I, uint64
                 const uint64_t *targets, uint64_t k, uint64_t *pos_out, uint64_t *n_total, int *stop,
                 int nthreads);
 }  // namespace gpd
-#include "../../include/gpd_afpacket.h"
 namespace gpd {
-// One user-owned block of a gpd_decode_tpv3 call, as the host planned it (gpd_afpacket.cpp).
-struct TwPlan {
-  uint32_t ring_block;  // index in the ring
-  uint32_t emit;        // packets the read loop returns from it
-  uint64_t out;         // index of its first packet in the call's output
-  uint64_t entry;       // its first emitted packet header (relative to the block)
-};
-// gpd_decode_tpv3 with the block walk on the device (gpd_runtime.cpp): the planned blocks
-// travel to HBM in groups of consecutive ring blocks, are walked there (gpd_tpv3walk.hip)
-// and decoded, and results and capture info come back.  *fallback: the device path does not
-// apply (tuning, geometry, a block the walk rejects, a tagged frame with add_vlan) and the
-// caller runs the host path for the whole call (nothing returned so far counts).
-int decode_tpv3_device(gpd_ctx *ctx, const gpd_tpv3_ring &R, const std::vector<TwPlan> &plan, uint64_t n,
-                       bool add_vlan, const gpd_tpv3_pkts *pk, const gpd_result *out, int nthreads,
-                       bool *fallback);
-
 // Multiplicative hash of a 16-bit key into 2^bits buckets (host and device must agree).
 __host__ __device__ inline uint32_t key_hash(uint32_t key, uint32_t mult, uint32_t bits) {
   return ((key * mult) & 0xFFFFu) >> (16 - bits);

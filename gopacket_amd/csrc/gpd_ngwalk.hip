@@ -5,7 +5,7 @@
 // header of the bulk of a capture.  A pcapng stream differs from pcap in that blocks change the
 // reader's state (a section header switches the byte order and clears the interfaces, an
 // interface description adds one, a statistics block can stop the reader), so the device walks
-// between such blocks only.  The host (gpd_runtime.cpp) hands each chunk the reader's state —
+// between such blocks only.  The host (gpd_capture.cpp) hands each chunk the reader's state —
 // the section's byte order, which interfaces exist and which of them keep their packets,
 // interface 0's snap length — and pcapng's rules are:
 //
