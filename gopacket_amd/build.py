@@ -32,13 +32,14 @@ SOURCES = [os.path.join(CSRC, "gpd_kernels.hip"), os.path.join(CSRC, "gpd_runtim
            os.path.join(CSRC, "gpd_pcap.cpp"), os.path.join(CSRC, "gpd_flow.hip"),
            os.path.join(CSRC, "gpd_pcapwalk.hip"), os.path.join(CSRC, "gpd_tpv3walk.hip"),
            os.path.join(CSRC, "gpd_afpacket.cpp"), os.path.join(CSRC, "gpd_pcapng.cpp"),
-           os.path.join(CSRC, "gpd_ngwalk.hip")]
+           os.path.join(CSRC, "gpd_ngwalk.hip"), os.path.join(CSRC, "gpd_pcapwrite.hip")]
 HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h"),
            os.path.join(CSRC, "gpd_segwalk.h"),
            os.path.join(ROOT, "include", "gpd.h"),
            os.path.join(ROOT, "include", "gpd_pcap.h"), os.path.join(ROOT, "include", "gpd_flow.h"),
            os.path.join(ROOT, "include", "gpd_afpacket.h"), os.path.join(ROOT, "include", "gpd_defrag.h"),
-           os.path.join(ROOT, "include", "gpd_pcapng.h"), os.path.join(CSRC, "gpd_pcapng_internal.h")]
+           os.path.join(ROOT, "include", "gpd_pcapng.h"), os.path.join(CSRC, "gpd_pcapng_internal.h"),
+           os.path.join(ROOT, "include", "gpd_pcapwrite.h")]
 
 
 def _stale(target, deps):

@@ -324,6 +324,21 @@ class DeviceBatch:
         self.offset, self.caplen = desc[:n], desc[n + pad:]
         self.device = device
 
+    @classmethod
+    def from_tensors(cls, data, data_len: int, offset, caplen, device: int = 0) -> "DeviceBatch":
+        """A batch already in HBM: `data` a uint8 tensor readable to round_up(data_len, 16),
+        `offset` and `caplen` int32 tensors of equal length (their bits are the uint32 values) on
+        `device`, kept by reference — for the placement above, pass two views of one allocation
+        with caplen[] right after offset[] (pcapwrite.select does)."""
+        if offset.numel() != caplen.numel():
+            raise ValueError("DeviceBatch.from_tensors: offset and caplen differ in length")
+        if data.numel() < (int(data_len) + 15) // 16 * 16:
+            raise ValueError("DeviceBatch.from_tensors: data must be readable to round_up(data_len, 16)")
+        self = cls.__new__(cls)
+        self.n, self.data_len, self.device = int(offset.numel()), int(data_len), device
+        self.data, self.offset, self.caplen = data, offset, caplen
+        return self
+
     def c_batch(self) -> GpdBatch:
         return GpdBatch(self.data.data_ptr(), self.data_len, self.offset.data_ptr(),
                         self.caplen.data_ptr(), self.n)
