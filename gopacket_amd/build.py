@@ -27,14 +27,18 @@ LIB = os.path.join(PKG, "libgpd.so")
 DIAG_LIB = os.path.join(PKG, "libgpd_diag.so")
 ORACLE_LIB = os.path.join(ROOT, "oracle", "libgpd_oracle.so")
 
-SOURCES = [os.path.join(CSRC, "gpd_kernels.hip"), os.path.join(CSRC, "gpd_runtime.cpp"),
+KERNEL_SOURCES = [os.path.join(CSRC, f) for f in  # the decode kernels: one TU per kernel family
+                  ("gpd_rs.hip", "gpd_kernels.hip", "gpd_ro.hip", "gpd_sp.hip")]
+SOURCES = [*KERNEL_SOURCES, os.path.join(CSRC, "gpd_runtime.cpp"),
            os.path.join(CSRC, "gpd_staging.cpp"), os.path.join(CSRC, "gpd_capture.cpp"),
            os.path.join(CSRC, "gpd_pcap.cpp"), os.path.join(CSRC, "gpd_flow.hip"),
            os.path.join(CSRC, "gpd_pcapwalk.hip"), os.path.join(CSRC, "gpd_tpv3walk.hip"),
            os.path.join(CSRC, "gpd_afpacket.cpp"), os.path.join(CSRC, "gpd_pcapng.cpp"),
            os.path.join(CSRC, "gpd_ngwalk.hip"), os.path.join(CSRC, "gpd_pcapwrite.hip")]
 HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h"),
-           os.path.join(CSRC, "gpd_segwalk.h"),
+           os.path.join(CSRC, "gpd_segwalk.h"), os.path.join(CSRC, "gpd_launch.h"),
+           os.path.join(CSRC, "gpd_dev_common.h"), os.path.join(CSRC, "gpd_dev_tables.h"),
+           os.path.join(CSRC, "gpd_dev_generic.h"), os.path.join(CSRC, "gpd_dev_fast.h"),
            os.path.join(ROOT, "include", "gpd.h"),
            os.path.join(ROOT, "include", "gpd_pcap.h"), os.path.join(ROOT, "include", "gpd_flow.h"),
            os.path.join(ROOT, "include", "gpd_afpacket.h"), os.path.join(ROOT, "include", "gpd_defrag.h"),
@@ -57,7 +61,7 @@ def build_lib(force: bool = False, verbose: bool = False, diag: bool = False) ->
         extra = os.environ.get("GPD_EXTRA_CFLAGS", "").split()  # A/B builds (tools/)
         if diag:
             extra.append("-DGPD_DIAG")
-        # one hipcc per source in parallel (the kernels' TU dominates), then one link
+        # one hipcc per source in parallel (rs_kernel's TU, listed first, dominates), then one link
         objdir = os.path.join(ROOT, "build", "diag" if diag else "lib")
         os.makedirs(objdir, exist_ok=True)
         base = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall",

@@ -220,6 +220,12 @@ constexpr uint64_t kMaxLaunchPackets = 1ull << 30;
 hipError_t launch_decode(const KParams &P, hipStream_t stream, int num_cus, hipEvent_t mid = nullptr,
                          uint32_t *fb_waves = nullptr);
 
+// The fast kernel families, one translation unit each (gpd_rs.hip, gpd_ro.hip, gpd_sp.hip):
+// launch the family's instance for P's window, options and tuning; P.fb_waves is set.
+hipError_t launch_fast_rs(KParams &P, hipStream_t stream, int num_cus);
+hipError_t launch_fast_ro(KParams &P, hipStream_t stream, int num_cus);
+hipError_t launch_fast_sp(KParams &P, hipStream_t stream, int num_cus);
+
 // Host side: set the thread's gpd_last_error_string() text and return `code` (gpd_runtime.cpp).
 int set_error(int code, const char *fmt, ...);
 

@@ -182,22 +182,30 @@ def test_fast_kernels_do_not_spill():
     bound without scratch spills: a spill puts global-memory traffic into the streaming loop
     (a one-line change to the decode once cost 15-85 spilled VGPRs and 10-20 % of IMIX/VXLAN)."""
     import tempfile
-    src = os.path.join(ROOT, "gopacket_amd", "csrc", "gpd_kernels.hip")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "k.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I",
-                        os.path.join(ROOT, "include"), "-S", "--cuda-device-only", src, "-o", out],
-                       check=True, capture_output=True, timeout=600)
-        txt = open(out).read()
-    seen = 0
+    from concurrent.futures import ThreadPoolExecutor
+    from gopacket_amd.build import KERNEL_SOURCES
+
+    def device_asm(src):  # one kernel translation unit's gfx950 assembly
+        with tempfile.TemporaryDirectory() as d:
+            out = os.path.join(d, "k.s")
+            subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I",
+                            os.path.join(ROOT, "include"), "-S", "--cuda-device-only", src, "-o", out],
+                           check=True, capture_output=True, timeout=600)
+            return open(out).read()
+
+    with ThreadPoolExecutor(max_workers=len(KERNEL_SOURCES)) as ex:
+        txt = "".join(ex.map(device_asm, KERNEL_SOURCES))
+    seen, families = 0, set()
     for b in txt.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", b).group(1)
         if "rs_kernel" not in name and "ro_kernel" not in name and "sp_kernel" not in name:
             continue
         seen += 1
+        families.add(re.search(r"(rs|ro|sp)_kernel", name).group(0))
         spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", b).group(1))
         assert spill == 0, f"{name}: {spill} VGPRs spilled"
     assert seen >= 20
+    assert families == {"rs_kernel", "ro_kernel", "sp_kernel"}
 
 
 def test_shipped_library_has_no_diagnostic_kernels():

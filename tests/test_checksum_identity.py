@@ -1,5 +1,5 @@
 """The fast path sums checksums in the little-endian domain (v_dot2_u32_u16 over raw words)
-and byte-swaps once at the end (gpd_kernels.hip fold_le_not).  This pins the identity it
+and byte-swaps once at the end (csrc/gpd_dev_common.h fold_le_not).  This pins the identity it
 relies on against tcpipChecksum's own fold (layers/tcpip.go:52-70): for any word sequence
 whose sums do not wrap 2^32, ~fold(sum of big-endian words) == swap16(~fold(sum of
 byte-swapped words)) — including the all-zero and 0xFFFF-multiple representatives."""

@@ -93,7 +93,7 @@ def run_both(batch, first=L.LayerTypeEthernet, mask=ALL, options=0, tables=None,
              tuning=None):
     """Device vs oracle.  With ext=True both kernels are checked: the ext records force the
     generic decoder, so the same batch is decoded again without them, which takes the fast
-    kernel + fallback list whenever it is eligible (gpd_kernels.hip fast_eligible)."""
+    kernel + fallback list whenever it is eligible (csrc/gpd_kernels.hip fast_eligible)."""
     ref = O.decode(batch, first, mask, options, tables=tables, ext=ext, nthreads=8)
     out = None
     for e in ((True, False) if ext else (False,)):
@@ -1137,7 +1137,7 @@ def test_llc_frames_in_every_kernel(ho):
     """802.3 length framing among long frames: Length below, at and above the captured payload,
     0..4 bytes of LLC, SNAP / STP / other SAP pairs, one- and two-byte control fields
     (ethernet.go:53-58, llc.go:31-69) — the header-once tile decode takes these frames itself
-    (gpd_kernels.hip fast_decode<HO>, the et0 < 0x0600 exit), the windowed kernels leave them to
+    (csrc/gpd_dev_fast.h fast_decode<HO>, the et0 < 0x0600 exit), the windowed kernels leave them to
     the generic decoder; with LLC registered and not, against the oracle."""
     rng = np.random.default_rng(77 + ho)
     base = synth.make_imix(1 << 12)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build A/B variant trees ab_e<N>/ (a copy of the working tree whose libgpd.so is compiled with
-# -DGPD_EXP=<N>, gpd_kernels.hip kExp* bits) for tools/ab_exp.sh.  Runs on the CPU container.
+# -DGPD_EXP=<N>, the `#if GPD_EXP & ...` blocks of csrc/gpd_dev_*.h) for tools/ab_exp.sh.  Runs on the CPU container.
 # usage: tools/ab_exp_build.sh N [N ...]
 set -eu
 cd "$(dirname "$0")/.."

@@ -1,7 +1,7 @@
-"""Instruction mix of the fast kernels in a gpd_kernels.hip build (device assembly), to compare
-builds on the CPU before a GPU A/B: the register allocator's choices move VALU counts by several
-percent between near-identical sources.
-    python tools/isa_count.py [path/to/gpd_kernels.hip] [-DFLAG ...]"""
+"""Instruction mix of rs_kernel's main instances in a gpd_rs.hip build (device assembly), to
+compare builds on the CPU before a GPU A/B: the register allocator's choices move VALU counts by
+several percent between near-identical sources (tools/isa_diff.py: are two builds the same?).
+    python tools/isa_count.py [path/to/gpd_rs.hip] [-DFLAG ...]"""
 import collections
 import os
 import re
@@ -9,7 +9,7 @@ import subprocess
 import sys
 
 src = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".hip") else \
-    os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gopacket_amd/csrc/gpd_kernels.hip")
+    os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gopacket_amd/csrc/gpd_rs.hip")
 flags = [a for a in sys.argv[1:] if a.startswith("-D")]
 inc = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(src))), "include")
 out = "/tmp/isa_count.s"
