@@ -4,8 +4,8 @@ The product path is libgpd.so (HIP kernels for gfx950 behind the C-ABI in
 include/gpd.h); this package is the host-side mirror of gopacket's parser API
 (parser.py), its dispatch tables (layers.py), batch layout (batch.py), result
 reading (results.py), input formats (pcap.py, pcapng.py, afpacket.py, synth.py), the pcap
-writer and batch selection (pcapwrite.py), the flow table (flows.py) and the IPv4 fragment
-hand-off to ip4defrag (defrag.py).  (The stateful
+writer and batch selection (pcapwrite.py), BPF filtering of a device batch (bpf.py), the flow
+table (flows.py) and the IPv4 fragment hand-off to ip4defrag (defrag.py).  (The stateful
 reassembly over that hand-off is restated only as a test checker, oracle/ip4defrag_ref.py:
 ip4defrag itself is out of scope.)
 """
@@ -18,13 +18,13 @@ from .results import (BatchResult, Endpoint, FastHashes, Flow, FlowFromEndpoints
 
 __all__ = ["layers", "PacketBatch", "BatchResult", "DecodeError", "UnsupportedLayerType",
            "Endpoint", "Flow", "NewEndpoint", "NewFlow", "FlowFromEndpoints", "FastHashes",
-           "MaxEndpointSize", "parser", "pcapng", "pcapwrite"]
+           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf"]
 
 
 def __getattr__(name):
     # the parser pulls in libgpd.so; import it lazily so that pure-host helpers
     # (pcap, synth, layers) work in environments that only build.
-    if name in ("parser", "pcapng", "pcapwrite"):  # (pcapng and pcapwrite bind their entry points onto libgpd.so too)
+    if name in ("parser", "pcapng", "pcapwrite", "bpf"):  # (pcapng, pcapwrite and bpf bind their entry points onto libgpd.so too)
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

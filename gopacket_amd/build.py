@@ -34,7 +34,8 @@ SOURCES = [*KERNEL_SOURCES, os.path.join(CSRC, "gpd_runtime.cpp"),
            os.path.join(CSRC, "gpd_pcap.cpp"), os.path.join(CSRC, "gpd_flow.hip"),
            os.path.join(CSRC, "gpd_pcapwalk.hip"), os.path.join(CSRC, "gpd_tpv3walk.hip"),
            os.path.join(CSRC, "gpd_afpacket.cpp"), os.path.join(CSRC, "gpd_pcapng.cpp"),
-           os.path.join(CSRC, "gpd_ngwalk.hip"), os.path.join(CSRC, "gpd_pcapwrite.hip")]
+           os.path.join(CSRC, "gpd_ngwalk.hip"), os.path.join(CSRC, "gpd_pcapwrite.hip"),
+           os.path.join(CSRC, "gpd_bpf.hip"), os.path.join(CSRC, "gpd_bpf_host.cpp")]
 HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h"),
            os.path.join(CSRC, "gpd_segwalk.h"), os.path.join(CSRC, "gpd_launch.h"),
            os.path.join(CSRC, "gpd_dev_common.h"), os.path.join(CSRC, "gpd_dev_tables.h"),
@@ -43,7 +44,8 @@ HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h")
            os.path.join(ROOT, "include", "gpd_pcap.h"), os.path.join(ROOT, "include", "gpd_flow.h"),
            os.path.join(ROOT, "include", "gpd_afpacket.h"), os.path.join(ROOT, "include", "gpd_defrag.h"),
            os.path.join(ROOT, "include", "gpd_pcapng.h"), os.path.join(CSRC, "gpd_pcapng_internal.h"),
-           os.path.join(ROOT, "include", "gpd_pcapwrite.h")]
+           os.path.join(ROOT, "include", "gpd_pcapwrite.h"), os.path.join(ROOT, "include", "gpd_bpf.h"),
+           os.path.join(CSRC, "gpd_bpf_vm.h"), os.path.join(CSRC, "gpd_bpf_host.h")]
 
 
 def _stale(target, deps):
