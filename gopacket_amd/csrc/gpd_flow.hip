@@ -730,11 +730,11 @@ int gpd_flow_reset(gpd_flowtable *ft, void *stream) {
 
 int gpd_flow_insert(gpd_flowtable *ft, const gpd_batch *in, const gpd_result *res,
                     uint32_t *flow_id, uint64_t index_base, void *stream) {
-  if (!ft || !in || !res || !flow_id)
+  if (!ft || !in || !res || (in->n && !flow_id))
     return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_insert: null argument");
+  if (in->n == 0) return GPD_OK;  // (an empty batch's arrays may be null: nothing is read)
   if (!(res->status || res->records) || !res->hdr_off)
     return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_insert: the results need status (or records) and hdr_off");
-  if (in->n == 0) return GPD_OK;
   if (!in->data || !in->offset || !in->caplen)
     return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_insert: null batch array");
   gpd::DeviceScope dscope_;
@@ -768,11 +768,11 @@ int gpd_flow_keys(gpd_flowtable *ft, const gpd_batch *in, const gpd_result *res,
   if (nparts == 0 || nparts > GPD_FLOW_MAX_PARTS)
     return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_keys: nparts %u outside [1, %d]", nparts,
                           GPD_FLOW_MAX_PARTS);
+  for (uint32_t p = 0; p < nparts; p++) part_count[p] = 0;
+  if (in->n == 0) return GPD_OK;  // (an empty batch's arrays may be null: nothing is read)
   if (!res->hdr_off || !(res->records || (res->status && res->net_hash && res->tp_hash)))
     return gpd::set_error(GPD_ERR_INVALID,
                           "gpd_flow_keys: the results need hdr_off and records, or status, net_hash and tp_hash");
-  for (uint32_t p = 0; p < nparts; p++) part_count[p] = 0;
-  if (in->n == 0) return GPD_OK;
   if (!in->data || !in->offset || !in->caplen)
     return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_keys: null batch array");
   gpd::DeviceScope dscope_;

@@ -84,7 +84,9 @@ int gpd_flow_reset(gpd_flowtable *ft, void *stream);
 /* Find-or-create the flow of every packet of a decoded batch (device pointers): `in` is the
  * batch gpd_decode read, `res` its results (hdr_off, and status or the gpd_record form), flow_id[n] receives
  * each packet's record index (or a GPD_FLOW_* value).  Packet i counts as sequence number
- * index_base + i.  Asynchronous on `stream`; the batch must be decoded on that stream first. */
+ * index_base + i.  Asynchronous on `stream`; the batch must be decoded on that stream first.
+ * An empty batch (in->n == 0) is a no-op, here and in gpd_flow_keys (every count 0): its
+ * batch, result and output arrays may be null. */
 int gpd_flow_insert(gpd_flowtable *ft, const gpd_batch *in, const gpd_result *res,
                     uint32_t *flow_id, uint64_t index_base, void *stream);
 /* Counters since the last reset (synchronises `stream`). */
