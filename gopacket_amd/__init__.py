@@ -5,9 +5,10 @@ include/gpd.h); this package is the host-side mirror of gopacket's parser API
 (parser.py), its dispatch tables (layers.py), batch layout (batch.py), result
 reading (results.py), input formats (pcap.py, pcapng.py, afpacket.py, synth.py), the pcap
 writer and batch selection (pcapwrite.py), BPF filtering of a device batch (bpf.py), the flow
-table (flows.py) and the IPv4 fragment hand-off to ip4defrag (defrag.py).  (The stateful
-reassembly over that hand-off is restated only as a test checker, oracle/ip4defrag_ref.py:
-ip4defrag itself is out of scope.)
+table (flows.py), the IPv4 fragment hand-off to ip4defrag (defrag.py) and the TCP segment
+hand-off to tcpassembly (tcpassembly.py).  (The stateful consumers of the two hand-offs are
+restated only as test checkers, oracle/ip4defrag_ref.py and tests/tcpassembly_ref.py: ip4defrag
+and the stream assembler themselves are out of scope.)
 """
 from . import layers
 from .layers import *  # noqa: F401,F403  LayerType constants, Register*PortLayerType
@@ -18,13 +19,14 @@ from .results import (BatchResult, Endpoint, FastHashes, Flow, FlowFromEndpoints
 
 __all__ = ["layers", "PacketBatch", "BatchResult", "DecodeError", "UnsupportedLayerType",
            "Endpoint", "Flow", "NewEndpoint", "NewFlow", "FlowFromEndpoints", "FastHashes",
-           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf"]
+           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly"]
 
 
 def __getattr__(name):
     # the parser pulls in libgpd.so; import it lazily so that pure-host helpers
     # (pcap, synth, layers) work in environments that only build.
-    if name in ("parser", "pcapng", "pcapwrite", "bpf"):  # (pcapng, pcapwrite and bpf bind their entry points onto libgpd.so too)
+    # (pcapng, pcapwrite, bpf and tcpassembly bind their entry points onto libgpd.so too)
+    if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -35,9 +35,11 @@ SOURCES = [*KERNEL_SOURCES, os.path.join(CSRC, "gpd_runtime.cpp"),
            os.path.join(CSRC, "gpd_pcapwalk.hip"), os.path.join(CSRC, "gpd_tpv3walk.hip"),
            os.path.join(CSRC, "gpd_afpacket.cpp"), os.path.join(CSRC, "gpd_pcapng.cpp"),
            os.path.join(CSRC, "gpd_ngwalk.hip"), os.path.join(CSRC, "gpd_pcapwrite.hip"),
-           os.path.join(CSRC, "gpd_bpf.hip"), os.path.join(CSRC, "gpd_bpf_host.cpp")]
+           os.path.join(CSRC, "gpd_bpf.hip"), os.path.join(CSRC, "gpd_bpf_host.cpp"),
+           os.path.join(CSRC, "gpd_tcpseg.hip")]
 HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h"),
            os.path.join(CSRC, "gpd_segwalk.h"), os.path.join(CSRC, "gpd_launch.h"),
+           os.path.join(CSRC, "gpd_compact.h"),
            os.path.join(CSRC, "gpd_dev_common.h"), os.path.join(CSRC, "gpd_dev_tables.h"),
            os.path.join(CSRC, "gpd_dev_generic.h"), os.path.join(CSRC, "gpd_dev_fast.h"),
            os.path.join(ROOT, "include", "gpd.h"),
@@ -45,7 +47,8 @@ HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h")
            os.path.join(ROOT, "include", "gpd_afpacket.h"), os.path.join(ROOT, "include", "gpd_defrag.h"),
            os.path.join(ROOT, "include", "gpd_pcapng.h"), os.path.join(CSRC, "gpd_pcapng_internal.h"),
            os.path.join(ROOT, "include", "gpd_pcapwrite.h"), os.path.join(ROOT, "include", "gpd_bpf.h"),
-           os.path.join(CSRC, "gpd_bpf_vm.h"), os.path.join(CSRC, "gpd_bpf_host.h")]
+           os.path.join(CSRC, "gpd_bpf_vm.h"), os.path.join(CSRC, "gpd_bpf_host.h"),
+           os.path.join(ROOT, "include", "gpd_tcpassembly.h")]
 
 
 def _stale(target, deps):

@@ -152,7 +152,7 @@ struct gpd_ctx {
   struct Scratch {
     void *d = nullptr;
     size_t bytes = 0;
-  } scratch[16];
+  } scratch[17];
   gpd_tuning tune{0, -1, -1, 0, -1, -1, 0, -1};  // gpd_ctx_set_tuning (all automatic by default)
   bool timing = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr;
@@ -179,9 +179,6 @@ struct gpd_ctx {
 };
 
 namespace gpd {
-
-// The table image and the option fields of P from the context (gpd_runtime.cpp).
-void ctx_fill_kparams(const gpd_ctx *ctx, KParams &P);
 
 // The decode launch (gpd_runtime.cpp).  n_dev: the packet count is read on the device (at most
 // in->n); geom_n: the packet count the staging choices assume (0: in->n) — both for batches

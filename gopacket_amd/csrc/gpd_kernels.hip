@@ -16,6 +16,7 @@
 // decoder per packet, the generic one for the packets it leaves — and decode_kernel otherwise.
 #include <hip/hip_runtime.h>
 
+#include "gpd_compact.h"
 #include "gpd_dev_generic.h"
 #include "gpd_launch.h"
 
@@ -266,71 +267,17 @@ __device__ __forceinline__ bool frag_candidate(const KParams &P, uint32_t i) {
   return (flags & 1u) || fo != 0;
 }
 
-// Packets per counting workgroup: 8 rounds of 256 lanes; bit l of mask word w is packet 64w + l.
-constexpr uint32_t kFragBlock = 2048;
-
+// The compaction (gpd_compact.h, shared with the tcpassembly hand-off): candidate bits and
+// per-block counts, their exclusive scan, the candidates' packet indices in order (fragments are
+// rare: the index pass usually writes nothing at all).
 __global__ __launch_bounds__(256) void frag_count_kernel(FragArgs A) {
-  __shared__ uint32_t wsum[4];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint32_t base = blockIdx.x * kFragBlock;
-  uint32_t c = 0;
-#pragma unroll 2
-  for (uint32_t r = 0; r < kFragBlock / 256u; ++r) {
-    const uint32_t i = base + r * 256u + threadIdx.x;
-    const uint64_t m = __ballot(i < A.P.n && frag_candidate(A.P, i));
-    if (lane == 0 && base + r * 256u + w * 64u < A.P.n) A.mask[(base + r * 256u) / 64u + w] = m;
-    c += (uint32_t)__popcll(m);
-  }
-  if (lane == 0) wsum[w] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) A.blk[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  compact_count((uint32_t)A.P.n, A.mask, A.blk, [&A](uint32_t i) { return frag_candidate(A.P, i); });
 }
 
-// One workgroup: exclusive scan of the per-block counts in place, 1024 at a time (coalesced);
-// blk[nblk] = the total.
-__global__ __launch_bounds__(1024) void frag_scan_kernel(FragArgs A) {
-  __shared__ uint32_t wtot[16];
-  __shared__ uint32_t carry;
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (uint32_t c0 = 0; c0 < A.nblk; c0 += 1024u) {
-    const uint32_t k = c0 + t;
-    const uint32_t v = k < A.nblk ? A.blk[k] : 0u;
-    uint32_t x = v;  // inclusive scan within the wave
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t y = __shfl_up(x, d, 64);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63u) wtot[w] = x;
-    __syncthreads();
-    uint32_t before = carry;
-    for (uint32_t j = 0; j < w; ++j) before += wtot[j];
-    if (k < A.nblk) A.blk[k] = before + x - v;
-    __syncthreads();
-    if (t == 1023u) carry = before + x;
-    __syncthreads();
-  }
-  if (t == 0) A.blk[A.nblk] = carry;
-}
+__global__ __launch_bounds__(1024) void frag_scan_kernel(FragArgs A) { compact_scan(A.blk, A.nblk); }
 
-// The candidates' packet indices in order, from the mask words: 32 words per block, one lane
-// each; a lane writes its word's set bits (fragments are rare: usually nothing at all).
 __global__ __launch_bounds__(64) void frag_index_kernel(FragArgs A) {
-  const uint32_t lane = threadIdx.x;
-  const uint32_t wi = blockIdx.x * (kFragBlock / 64u) + lane;
-  const uint32_t nw = (A.P.n + 63u) / 64u;
-  const uint64_t m = (lane < kFragBlock / 64u && wi < nw) ? A.mask[wi] : 0ull;
-  if (__ballot(m != 0ull) == 0ull) return;
-  uint32_t x = (uint32_t)__popcll(m), v = x;
-#pragma unroll
-  for (uint32_t d = 1; d < 64u; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  uint32_t r = A.blk[blockIdx.x] + x - v;
-  for (uint64_t b = m; b; b &= b - 1ull) A.idx[r++] = wi * 64u + (uint32_t)__builtin_ctzll(b);
+  compact_index(A.blk, A.mask, A.idx, (uint32_t)A.P.n);
 }
 
 // One lane per candidate: the generic decoder re-runs the packet for the IPv4 object's exact

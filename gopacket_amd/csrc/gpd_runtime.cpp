@@ -178,7 +178,7 @@ namespace gpd {
 int ctx_device(const gpd_ctx *ctx) { return ctx->device; }
 int ctx_num_cus(const gpd_ctx *ctx) { return ctx->num_cus; }
 void *ctx_scratch(gpd_ctx *ctx, int slot, size_t bytes) {
-  if (slot < 0 || slot >= 16) return nullptr;
+  if (slot < 0 || slot >= (int)(sizeof ctx->scratch / sizeof ctx->scratch[0])) return nullptr;
   auto &sc = ctx->scratch[slot];
   if (sc.bytes < bytes) {
     if (sc.d) (void)hipFree(sc.d);

@@ -1,0 +1,493 @@
+// gpd_tcpseg.hip — the tcpassembly hand-off (include/gpd_tcpassembly.h): the TCP segments of a
+// decoded device batch that Assembler.AssembleWithTimestamp acts on
+// (tcpassembly/assembly.go:533-607), each with what that call reads from the TCP layer, in
+// packet order or grouped by flow record (the assembler's key, :289,543), stably.
+//
+// The hand-over is the fragment hand-off's ordered compaction (gpd_compact.h, one copy for both): per-2048-packet
+// counts and one bit per packet, their exclusive scan by one workgroup, the kept packets'
+// indices in order, and one record per kept packet.  Grouping adds the project's first device
+// sort, an LSD radix sort of (key, segment index) pairs, key = min(flow_id, id_bound), 8 bits a
+// pass.  Each pass is three launches and no kernel waits on another workgroup (no decoupled
+// look-back, no spin on a global word): passes are separated by launch boundaries only.
+//
+//   ts_count_kernel     one lane per packet: is it handed over?  (mask bit, per-block count)
+//   ts_scan_kernel      one workgroup: exclusive scan of the block counts
+//   ts_index_kernel     the kept packets' indices in order, from the mask words
+//   ts_record_kernel    one lane per segment: the 32-byte record (in packet order), and with
+//                       grouping its (key, index) pair
+//   sort_hist_kernel    per workgroup tile of kSortTile pairs: counts per digit, [digit][tile]
+//   sort_scan_kernel    one workgroup: exclusive scan of the [digit][tile] counts in place
+//   sort_scatter_kernel stable ranks inside the tile: per wave eight ballots give the lanes
+//                       with the same digit, the rank is the popcount below the lane, and the
+//                       waves' bases are scanned in wave order through LDS.  The last pass
+//                       gathers the 32-byte records to their final places instead of the pairs.
+//   ts_head_kernel      head flags where the sorted key changes (the same count/scan/index)
+//   ts_group_kernel     one lane per group: its gpd_tcp_group
+//
+// Where t.Payload lies.  For the plain stacks — Ethernet, 802.1Q tags, IPv4 or IPv6 (no
+// hop-by-hop header), TCP — the record reads the network header and trims as the decoders do:
+// IPv4 Length (0 => len(data)) against the captured bytes (ip4.go:214-236), IPv6 Length
+// against them (ip6.go:270-275).  Every other stack (VXLAN, extension headers, a packet whose
+// decode ended in an error or past 12 layers) is run through the generic decoder again for the
+// TCP object's exact BaseLayer, as the fragment hand-off does for the IPv4 object.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "gpd_compact.h"
+#include "gpd_dev_generic.h"
+#include "../../include/gpd_flow.h"
+#include "../../include/gpd_tcpassembly.h"
+
+namespace gpd {
+namespace {
+
+static_assert(sizeof(gpd_tcp_seg) == 32 && sizeof(gpd_tcp_group) == 16, "include/gpd_tcpassembly.h layouts");
+
+constexpr uint32_t kCountBlock = kCompactBlock;  // items per counting workgroup
+constexpr uint32_t kSortThreads = 1024;
+constexpr uint32_t kSortWaves = kSortThreads / 64u;
+constexpr uint32_t kSortRounds = 8;     // pairs per lane
+constexpr uint32_t kSortTile = kSortThreads * kSortRounds;  // pairs per workgroup (tcpassembly.SORT_TILE)
+constexpr uint32_t kWaveSpan = 64u * kSortRounds;           // consecutive pairs of one wave
+
+struct TsArgs {
+  KParams P;
+  const uint32_t *flow_id;  // may be NULL
+  uint32_t id_bound;
+  uint32_t cnt;             // handed-over segments (known on the host after the scan)
+  gpd_tcp_seg *segs;        // the caller's
+  gpd_tcp_group *groups;
+  // scratch of the context
+  uint32_t nblk;            // blocks of the compaction in flight
+  uint32_t *blk;            // nblk + 1: per-block counts -> exclusive prefix; [nblk] = total
+  uint64_t *mask;           // one bit per item
+  uint32_t *idx;            // the kept items in order
+  gpd_tcp_seg *tmp;         // grouping: the records in packet order
+  uint2 *pa, *pb;           // ping-pong (key, segment index) pairs
+  uint32_t *hist;           // [256][tiles]
+  uint32_t *skey;           // the keys in final order
+  uint64_t *res;            // [0] groups, [1] ungrouped
+  uint32_t ntile;
+};
+
+__device__ __forceinline__ uint32_t be16p(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
+__device__ __forceinline__ uint32_t be32p(const uint8_t *p) {
+  return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+}
+
+// Packet i's segment record; false when it is not handed over.  The candidates are the packets
+// the flow table keys (gpd_flow.hip flow_key) whose transport endpoint type is TCPPort.
+template <bool PAGES>
+__device__ __forceinline__ bool tcp_segment(const KParams &P, const Tab<PAGES> &T, uint32_t options, uint32_t i,
+                                            gpd_tcp_seg &r) {
+  uint32_t st;
+  uint64_t lw;
+  if (P.rec) {
+    st = P.rec[i].status;
+    lw = P.rec[i].layers;
+  } else {
+    st = P.status[i];
+    lw = P.layers[i];
+  }
+  const uint32_t ho = P.hdr_off[i];
+  const uint32_t nt = GPD_STATUS_NET_EPT(st), tt = GPD_STATUS_TP_EPT(st);
+  const uint32_t no = GPD_HDR_NET(ho), to = GPD_HDR_TP(ho);
+  if (nt == 0 || tt != 4u || no == GPD_HDR_NONE || to == GPD_HDR_NONE) return false;
+  const uint32_t dlen = (uint32_t)P.data_len;
+  const uint32_t off = min(P.offset[i], dlen), len = min(P.caplen[i], dlen - off);
+  const uint8_t *pkt = P.data + off;
+  uint32_t c_off = to, p_off = 0, p_len = 0;
+  bool have = false;
+  const uint32_t nl = GPD_STATUS_NLAYERS(st);
+  if (P.first == GPD_LT_ETHERNET && GPD_STATUS_CLASS(st) != GPD_ST_DECODE_ERROR && !GPD_STATUS_SATURATED(st) &&
+      nl >= 3 && nl <= GPD_CORE_MAX_LAYERS && GPD_LAYERS_CODE(lw, 0) == GPD_C_ETHERNET) {
+    uint32_t k = 1;
+    while (k < nl && GPD_LAYERS_CODE(lw, k) == GPD_C_DOT1Q) ++k;
+    const uint32_t net = k < nl ? GPD_LAYERS_CODE(lw, k) : 0u;
+    const bool tail = k + 2 == nl || (k + 3 == nl && GPD_LAYERS_CODE(lw, k + 2) == GPD_C_PAYLOAD);
+    const uint32_t ipo = 14u + 4u * (k - 1u);
+    if ((net == GPD_C_IPV4 || net == GPD_C_IPV6) && k + 1 < nl && GPD_LAYERS_CODE(lw, k + 1) == GPD_C_TCP && tail &&
+        no == ipo && be16p(pkt + 12) >= 0x0600u) {  // (a length-typed frame trims: ethernet.go:50-57)
+      const uint8_t *h = pkt + ipo;
+      const uint32_t l0 = len - ipo;
+      uint32_t tcp_at = 0, tlen = 0;
+      if (net == GPD_C_IPV4) {  // ip4.go:214-236
+        uint32_t length = be16p(h + 2);
+        if (length == 0) length = l0 & 0xFFFFu;
+        const uint32_t hl = (h[0] & 0x0Fu) * 4u, d = l0 > length ? length : l0;
+        tcp_at = ipo + hl;
+        tlen = d - hl;
+      } else if (h[6] != 0) {  // ip6.go:270-275 (a hop-by-hop header is parsed inside: generic)
+        const uint32_t length = be16p(h + 4);
+        tlen = l0 - 40u;
+        if (length <= tlen) tlen = length;
+        tcp_at = ipo + 40u;
+      }
+      if (tcp_at == to && tlen <= len) {
+        const uint32_t ds = (uint32_t)(pkt[to + 12] >> 4) * 4u;
+        if (ds >= 20u && ds <= tlen) {
+          p_off = to + ds;
+          p_len = tlen - ds;
+          have = true;
+        }
+      }
+    }
+  }
+  if (!have) {
+    gpd_ext_rec e;
+    decode_packet<true>(GlbSrc{P.data, off}, len, T, P.first,
+                        options | GPD_OPT_NO_CHECKSUMS | GPD_OPT_NO_FLOW_HASH, &e);
+    if (!(e.obj_valid & (1u << GPD_OBJ_TCP))) return false;
+    c_off = e.obj[GPD_OBJ_TCP].contents_off;
+    p_off = e.obj[GPD_OBJ_TCP].payload_off;
+    p_len = e.obj[GPD_OBJ_TCP].payload_len;
+  }
+  const uint8_t *t = pkt + to;  // the header t's fields were last read from (gpd.h hdr_off)
+  const uint32_t flags = be16p(t + 12) & 0x1FFu;
+  if (!(flags & (GPD_TCP_SYN | GPD_TCP_FIN | GPD_TCP_RST)) && p_len == 0) return false;  // assembly.go:535
+  r.packet = i;
+  r.flow_id = GPD_FLOW_NONE;
+  r.seq = be32p(t + 4);
+  r.ack = be32p(t + 8);
+  r.payload_off = p_off;
+  r.payload_len = p_len;
+  r.tcp_off = (uint16_t)c_off;
+  r.flags = (uint16_t)flags;
+  r.lookup_only = (uint8_t)(!(flags & GPD_TCP_SYN) && p_len == 0);  // :550-551
+  r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
+  return true;
+}
+
+// ---- ordered compaction: count, scan, index (gpd_compact.h) -----------------------------------
+template <bool PAGES>
+__global__ __launch_bounds__(256) void ts_count_kernel(TsArgs A) {
+  const KParams &P = A.P;
+  for (uint32_t k = threadIdx.x; k < P.image_words; k += 256) reinterpret_cast<uint32_t *>(g_lds)[k] = P.image[k];
+  __syncthreads();
+  const Tab<PAGES> T = make_tab<PAGES>(P);
+  const uint32_t options = P.options & ~kDiagMask;
+  compact_count((uint32_t)P.n, A.mask, A.blk, [&](uint32_t i) {
+    gpd_tcp_seg rec;
+    return tcp_segment<PAGES>(P, T, options, i, rec);
+  });
+}
+
+// Head flags of the sorted keys: item r starts a group when its key differs from r - 1's.
+__global__ __launch_bounds__(256) void ts_head_kernel(TsArgs A) {
+  compact_count(A.cnt, A.mask, A.blk, [&A](uint32_t i) { return i == 0 || A.skey[i] != A.skey[i - 1]; });
+}
+
+__global__ __launch_bounds__(1024) void ts_scan_kernel(TsArgs A) { compact_scan(A.blk, A.nblk); }
+
+__global__ __launch_bounds__(64) void ts_index_kernel(TsArgs A, uint32_t nitems) {
+  compact_index(A.blk, A.mask, A.idx, nitems);
+}
+
+// One lane per handed-over packet, in packet order: its record, to the caller's array or (with
+// grouping) to the scratch the last sort pass gathers from, and its (key, index) pair.
+template <bool PAGES>
+__global__ __launch_bounds__(256) void ts_record_kernel(TsArgs A) {
+  const KParams &P = A.P;
+  for (uint32_t k = threadIdx.x; k < P.image_words; k += 256) reinterpret_cast<uint32_t *>(g_lds)[k] = P.image[k];
+  __syncthreads();
+  const Tab<PAGES> T = make_tab<PAGES>(P);
+  const uint32_t options = P.options & ~kDiagMask;
+  gpd_tcp_seg *dst = A.flow_id ? A.tmp : A.segs;
+  for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < A.cnt; j += gridDim.x * 256u) {
+    const uint32_t i = A.idx[j];
+    gpd_tcp_seg r{};
+    r.packet = i;
+    (void)tcp_segment<PAGES>(P, T, options, i, r);  // (true: the count kernel kept it)
+    if (A.flow_id) {
+      r.flow_id = A.flow_id[i];
+      A.pa[j] = make_uint2(min(r.flow_id, A.id_bound), j);
+    }
+    const uint4 *s = reinterpret_cast<const uint4 *>(&r);
+    uint4 *d = reinterpret_cast<uint4 *>(dst + j);
+    d[0] = s[0];
+    d[1] = s[1];
+  }
+}
+
+// ---- the radix sort ----------------------------------------------------------------------------
+// The lanes of the wave whose digit equals this lane's (invalid lanes match nobody): eight
+// ballots, one per bit.  Called by all 64 lanes.
+__device__ __forceinline__ uint64_t match_digit(bool valid, uint32_t d) {
+  uint64_t m = __ballot(valid);
+#pragma unroll
+  for (uint32_t b = 0; b < 8u; ++b) {
+    const bool bit = (d >> b) & 1u;
+    const uint64_t bal = __ballot(valid && bit);
+    m &= bit ? bal : ~bal;
+  }
+  return m;
+}
+
+// A wave owns kWaveSpan consecutive pairs of its workgroup's tile, lane l those at l, l + 64, ...
+__device__ __forceinline__ uint32_t tile_item(uint32_t w, uint32_t lane, uint32_t r) {
+  return blockIdx.x * kSortTile + w * kWaveSpan + r * 64u + lane;
+}
+
+__global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(TsArgs A, const uint2 *in, uint32_t shift) {
+  __shared__ uint32_t h[256];
+  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+  if (t < 256u) h[t] = 0;
+  __syncthreads();
+#pragma unroll
+  for (uint32_t r = 0; r < kSortRounds; ++r) {
+    const uint32_t j = tile_item(w, lane, r);
+    const bool valid = j < A.cnt;
+    const uint32_t d = valid ? (in[j].x >> shift) & 255u : 0u;
+    const uint64_t m = match_digit(valid, d);
+    if (valid && (m & ((1ull << lane) - 1ull)) == 0ull) atomicAdd(&h[d], (uint32_t)__popcll(m));
+  }
+  __syncthreads();
+  if (t < 256u) A.hist[t * A.ntile + blockIdx.x] = h[t];
+}
+
+// One workgroup: exclusive scan of hist[256 * ntile] in place, sixteen consecutive entries a lane
+// a round (16,384 entries between barriers: 2^24 pairs make 2^19 entries, 32 rounds).
+__global__ __launch_bounds__(1024) void sort_scan_kernel(TsArgs A) {
+  __shared__ uint32_t wtot[16];
+  __shared__ uint32_t carry;
+  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+  const uint32_t nent = 256u * A.ntile;  // a multiple of 16
+  if (t == 0) carry = 0;
+  __syncthreads();
+  for (uint32_t c0 = 0; c0 < nent; c0 += 16384u) {
+    const uint32_t k = c0 + 16u * t;
+    uint4 v[4];
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q) {
+      v[q] = k < nent ? *reinterpret_cast<const uint4 *>(A.hist + k + 4u * q) : make_uint4(0u, 0u, 0u, 0u);
+      s += v[q].x + v[q].y + v[q].z + v[q].w;
+    }
+    const uint32_t x = wave_scan32(s, lane);
+    if (lane == 63u) wtot[w] = x;
+    __syncthreads();
+    uint32_t before = carry;
+    for (uint32_t j = 0; j < w; ++j) before += wtot[j];
+    uint32_t e = before + x - s;
+    if (k < nent) {
+#pragma unroll
+      for (uint32_t q = 0; q < 4u; ++q) {
+        *reinterpret_cast<uint4 *>(A.hist + k + 4u * q) = make_uint4(e, e + v[q].x, e + v[q].x + v[q].y,
+                                                                     e + v[q].x + v[q].y + v[q].z);
+        e += v[q].x + v[q].y + v[q].z + v[q].w;
+      }
+    }
+    __syncthreads();
+    if (t == 1023u) carry = before + x;
+    __syncthreads();
+  }
+}
+
+// Stable scatter of one tile.  base[w][d] ends up as the place of wave w's first pair with digit
+// d: the tile's scanned [d][tile] word plus the counts of the waves before it; inside the wave a
+// pair's rank is the pairs of its digit in earlier rounds (the leader lane moves the base on)
+// plus the matching lanes below it.  LAST: the record of the pair's segment goes to its final
+// place, with the key beside it for the groups.
+template <bool LAST>
+__global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(TsArgs A, const uint2 *in, uint2 *out,
+                                                                      uint32_t shift) {
+  __shared__ uint32_t base[kSortWaves][256];
+  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+  for (uint32_t k = t; k < kSortWaves * 256u; k += kSortThreads) (&base[0][0])[k] = 0;
+  __syncthreads();
+  uint2 p[kSortRounds];
+  uint32_t below[kSortRounds], tot[kSortRounds];
+#pragma unroll
+  for (uint32_t r = 0; r < kSortRounds; ++r) {
+    const uint32_t j = tile_item(w, lane, r);
+    const bool valid = j < A.cnt;
+    p[r] = valid ? in[j] : make_uint2(0u, 0u);
+    const uint32_t d = (p[r].x >> shift) & 255u;
+    const uint64_t m = match_digit(valid, d);
+    below[r] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    tot[r] = (valid && below[r] == 0u) ? (uint32_t)__popcll(m) : 0u;  // the digit's leader lane
+    if (tot[r]) base[w][d] += tot[r];  // (one leader per digit: no two lanes on one word)
+    __builtin_amdgcn_wave_barrier();   // rounds stay in order across the wave's lanes
+  }
+  __syncthreads();
+  if (t < 256u) {
+    uint32_t b = A.hist[t * A.ntile + blockIdx.x];
+    for (uint32_t k = 0; k < kSortWaves; ++k) {
+      const uint32_t c = base[k][t];
+      base[k][t] = b;
+      b += c;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t r = 0; r < kSortRounds; ++r) {
+    const bool valid = tile_item(w, lane, r) < A.cnt;
+    const uint32_t d = (p[r].x >> shift) & 255u;
+    const uint32_t b = base[w][d];  // every lane reads before the leader moves it on
+    __builtin_amdgcn_wave_barrier();
+    if (tot[r]) base[w][d] = b + tot[r];
+    __builtin_amdgcn_wave_barrier();
+    if (valid) {
+      const uint32_t pos = b + below[r];
+      if (LAST) {
+        const uint4 *s = reinterpret_cast<const uint4 *>(A.tmp + p[r].y);
+        const uint4 s0 = s[0], s1 = s[1];
+        uint4 *q = reinterpret_cast<uint4 *>(A.segs + pos);
+        q[0] = s0;
+        q[1] = s1;
+        A.skey[pos] = p[r].x;
+      } else {
+        out[pos] = p[r];
+      }
+    }
+  }
+}
+
+// One lane per group: heads[g] (idx) is where it starts.  The last lane leaves the counts.
+__global__ __launch_bounds__(256) void ts_group_kernel(TsArgs A) {
+  const uint32_t ng = A.blk[A.nblk];
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  if (g >= ng) return;
+  const uint32_t r = A.idx[g], nxt = g + 1u < ng ? A.idx[g + 1u] : A.cnt;
+  const uint32_t key = A.skey[r];
+  const bool un = key >= A.id_bound;
+  A.groups[g] = gpd_tcp_group{un ? GPD_TCP_UNGROUPED : key, r, nxt - r, A.segs[r].packet};
+  if (g == ng - 1u) {
+    A.res[0] = ng;
+    A.res[1] = un ? nxt - r : 0u;
+  }
+}
+
+#define TS_TRY(expr)                                                                        \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
+  } while (0)
+
+inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+
+// Passes of the sort: ceil(bitlen(id_bound) / 8), at least one (keys lie in [0, id_bound]).
+inline uint32_t sort_passes(uint32_t id_bound) {
+  uint32_t bits = 0;
+  for (uint32_t v = id_bound; v; v >>= 1) ++bits;
+  return std::max(1u, (bits + 7u) / 8u);
+}
+
+}  // namespace
+}  // namespace gpd
+
+extern "C" int gpd_tcp_segments(gpd_ctx *ctx, const gpd_batch *in, const gpd_result *res,
+                                const uint32_t *flow_id, uint32_t id_bound,
+                                gpd_tcp_seg *segs, gpd_tcp_group *groups, uint64_t max_out,
+                                uint64_t *count, uint64_t *ngroups, uint64_t *ungrouped, void *stream) {
+  using namespace gpd;
+  const char *who = "gpd_tcp_segments";
+  if (!ctx || !in || !res || !count || !ngroups || !ungrouped)
+    return set_error(GPD_ERR_INVALID, "%s: null argument", who);
+  *count = *ngroups = *ungrouped = 0;
+  if (in->n > 0xFFFFFF00ull)
+    return set_error(GPD_ERR_INVALID, "%s: batch of %llu packets (max 2^32 - 256)", who, (unsigned long long)in->n);
+  if (max_out && !segs) return set_error(GPD_ERR_INVALID, "%s: null segs with max_out > 0", who);
+  if (segs && flow_id && !groups) return set_error(GPD_ERR_INVALID, "%s: grouping needs groups[]", who);
+  if (((uintptr_t)segs & 15u) || ((uintptr_t)groups & 15u))
+    return set_error(GPD_ERR_INVALID, "%s: segs and groups must be 16-byte aligned", who);
+  if (in->n == 0) return GPD_OK;
+  if (!in->data || !in->offset || !in->caplen)
+    return set_error(GPD_ERR_INVALID, "%s: batch data/offset/caplen must be non-NULL", who);
+  if (in->data_len >= 0xFFFFFFF0ull)
+    return set_error(GPD_ERR_INVALID, "%s: data_len %llu outside the 32-bit offset range", who,
+                     (unsigned long long)in->data_len);
+  if (!res->hdr_off || (!res->records && (!res->status || !res->layers)))
+    return set_error(GPD_ERR_INVALID, "%s: needs hdr_off and status + layers (or records)", who);
+  DeviceScope dscope_;
+  TS_TRY(dscope_.set(ctx_device(ctx)));
+  const hipStream_t s = (hipStream_t)stream;
+  TsArgs A{};
+  KParams &P = A.P;
+  P.data = in->data;
+  P.data_len = in->data_len;
+  P.offset = in->offset;
+  P.caplen = in->caplen;
+  P.n = in->n;
+  P.status = res->status;
+  P.layers = res->layers;
+  P.rec = res->records;
+  P.hdr_off = res->hdr_off;
+  ctx_fill_kparams(ctx, P);
+  A.flow_id = flow_id;
+  A.id_bound = id_bound;
+  A.segs = segs;
+  A.groups = groups;
+  // the compaction's scratch, sized by the batch: counts, mask, indices, the result words
+  const uint32_t n = (uint32_t)in->n;
+  A.nblk = (n + kCountBlock - 1u) / kCountBlock;
+  const size_t b_blk = up16(((size_t)A.nblk + 1) * 4), b_mask = up16(((size_t)n + 63) / 64 * 8);
+  auto *base = static_cast<uint8_t *>(ctx_scratch(ctx, 15, 16 + b_blk + b_mask + up16((size_t)n * 4)));
+  if (!base) return set_error(GPD_ERR_NOMEM, "%s: scratch allocation failed", who);
+  A.res = reinterpret_cast<uint64_t *>(base);
+  A.blk = reinterpret_cast<uint32_t *>(base + 16);
+  A.mask = reinterpret_cast<uint64_t *>(base + 16 + b_blk);
+  A.idx = reinterpret_cast<uint32_t *>(base + 16 + b_blk + b_mask);
+  const size_t lds = (P.image_words * 4u + 15u) & ~15u;
+  if (P.use_pages) hipLaunchKernelGGL(ts_count_kernel<true>, dim3(A.nblk), dim3(256), lds, s, A);
+  else hipLaunchKernelGGL(ts_count_kernel<false>, dim3(A.nblk), dim3(256), lds, s, A);
+  hipLaunchKernelGGL(ts_scan_kernel, dim3(1), dim3(1024), 0, s, A);
+  TS_TRY(hipGetLastError());
+  uint32_t total = 0;
+  TS_TRY(hipMemcpyAsync(&total, A.blk + A.nblk, 4, hipMemcpyDeviceToHost, s));
+  TS_TRY(hipStreamSynchronize(s));
+  *count = total;
+  if (!segs && !max_out) return GPD_OK;  // the sizing call
+  if (total > max_out)
+    return set_error(GPD_ERR_INVALID, "%s: %u segments, max_out is %llu", who, total, (unsigned long long)max_out);
+  if (total == 0) return GPD_OK;
+  A.cnt = total;
+  hipLaunchKernelGGL(ts_index_kernel, dim3(A.nblk), dim3(64), 0, s, A, n);
+  if (flow_id) {  // the sort's scratch, sized by the hand-off: records, two pair arrays, keys, counts
+    A.ntile = (total + kSortTile - 1u) / kSortTile;
+    const size_t b_tmp = (size_t)total * sizeof(gpd_tcp_seg), b_pair = up16((size_t)total * 8);
+    const size_t b_key = up16((size_t)total * 4), b_hist = (size_t)A.ntile * 256 * 4;
+    auto *sb = static_cast<uint8_t *>(ctx_scratch(ctx, 16, b_tmp + 2 * b_pair + b_key + b_hist));
+    if (!sb) return set_error(GPD_ERR_NOMEM, "%s: scratch allocation failed", who);
+    A.tmp = reinterpret_cast<gpd_tcp_seg *>(sb);
+    A.pa = reinterpret_cast<uint2 *>(sb + b_tmp);
+    A.pb = reinterpret_cast<uint2 *>(sb + b_tmp + b_pair);
+    A.skey = reinterpret_cast<uint32_t *>(sb + b_tmp + 2 * b_pair);
+    A.hist = reinterpret_cast<uint32_t *>(sb + b_tmp + 2 * b_pair + b_key);
+  }
+  const unsigned rgrid = (unsigned)std::min<uint64_t>((uint64_t)ctx_num_cus(ctx) * 8, (total + 255u) / 256u);
+  if (P.use_pages) hipLaunchKernelGGL(ts_record_kernel<true>, dim3(rgrid), dim3(256), lds, s, A);
+  else hipLaunchKernelGGL(ts_record_kernel<false>, dim3(rgrid), dim3(256), lds, s, A);
+  TS_TRY(hipGetLastError());
+  if (!flow_id) {
+    TS_TRY(hipStreamSynchronize(s));
+    return GPD_OK;
+  }
+  const uint32_t passes = sort_passes(id_bound);
+  uint2 *src = A.pa, *dst = A.pb;
+  for (uint32_t p = 0; p < passes; ++p) {
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(A.ntile), dim3(kSortThreads), 0, s, A, src, 8u * p);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, s, A);
+    if (p + 1 == passes)
+      hipLaunchKernelGGL(sort_scatter_kernel<true>, dim3(A.ntile), dim3(kSortThreads), 0, s, A, src, dst, 8u * p);
+    else
+      hipLaunchKernelGGL(sort_scatter_kernel<false>, dim3(A.ntile), dim3(kSortThreads), 0, s, A, src, dst, 8u * p);
+    std::swap(src, dst);
+  }
+  // the groups: the compaction again, over the sorted keys' head flags
+  A.nblk = (total + kCountBlock - 1u) / kCountBlock;
+  TS_TRY(hipMemsetAsync(A.res, 0, 16, s));
+  hipLaunchKernelGGL(ts_head_kernel, dim3(A.nblk), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(ts_scan_kernel, dim3(1), dim3(1024), 0, s, A);
+  hipLaunchKernelGGL(ts_index_kernel, dim3(A.nblk), dim3(64), 0, s, A, total);
+  hipLaunchKernelGGL(ts_group_kernel, dim3((total + 255u) / 256u), dim3(256), 0, s, A);
+  TS_TRY(hipGetLastError());
+  uint64_t out[2] = {0, 0};
+  TS_TRY(hipMemcpyAsync(out, A.res, 16, hipMemcpyDeviceToHost, s));
+  TS_TRY(hipStreamSynchronize(s));
+  *ngroups = out[0];
+  *ungrouped = out[1];
+  return GPD_OK;
+}

@@ -480,6 +480,49 @@ def make_mixed(n: int, seed: int = 0x5EED0005) -> PacketBatch:
     return PacketBatch.from_packets(pkts)
 
 
+# ---- single TCP segments, field by field (the tcpassembly hand-off's tests) ----------------
+def _csum16(b: bytes) -> int:
+    if len(b) & 1:
+        b += b"\x00"
+    s = sum((b[k] << 8) | b[k + 1] for k in range(0, len(b), 2))
+    while s >> 16:
+        s = (s & 0xFFFF) + (s >> 16)
+    return ~s & 0xFFFF
+
+
+def tcp_frame(src, dst, sport: int, dport: int, seq: int, ack: int = 0, flags: int = 0x10,
+              payload: bytes = b"", options: bytes = b"", tags: int = 0, ip_length=None,
+              pad_to: int = 0, doff=None) -> bytes:
+    """One Ethernet [802.1Q x tags] IPv4-or-IPv6 / TCP frame.  src, dst: 4 address bytes (IPv4)
+    or 16 (IPv6); flags: the 9 bits of header bytes 12..13; options: TCP option bytes (a
+    multiple of 4); ip_length: the IPv4 Length / IPv6 payload length field when it is not to be
+    the true one (0: TSO); pad_to: zero bytes appended up to that frame size (Ethernet padding);
+    doff: the data offset field when it is not to be the true one.  Checksums are valid for the
+    true lengths."""
+    src, dst = bytes(src), bytes(dst)
+    assert len(src) == len(dst) and len(src) in (4, 16) and len(options) % 4 == 0
+    hl = 20 + len(options)
+    d = hl // 4 if doff is None else int(doff)
+    tcp = (int(sport).to_bytes(2, "big") + int(dport).to_bytes(2, "big") + (seq & 0xFFFFFFFF).to_bytes(4, "big") +
+           (ack & 0xFFFFFFFF).to_bytes(4, "big") + bytes([(d << 4) | ((flags >> 8) & 1), flags & 0xFF]) +
+           (0x2000).to_bytes(2, "big") + b"\x00\x00\x00\x00" + bytes(options) + bytes(payload))
+    pseudo = src + dst + (b"\x00\x06" + len(tcp).to_bytes(2, "big") if len(src) == 4
+                          else len(tcp).to_bytes(4, "big") + b"\x00\x00\x00\x06")
+    tcp = tcp[:16] + _csum16(pseudo + tcp).to_bytes(2, "big") + tcp[18:]
+    eth = bytes([2, 0, 0, 0, 0, 2, 2, 0, 0, 0, 0, 1])
+    for t in range(tags):
+        eth += b"\x81\x00" + (t + 1).to_bytes(2, "big")
+    if len(src) == 4:
+        length = 20 + len(tcp) if ip_length is None else int(ip_length)
+        ip = bytes([0x45, 0]) + length.to_bytes(2, "big") + b"\x00\x01\x40\x00\x40\x06\x00\x00" + src + dst
+        ip = ip[:10] + _csum16(ip).to_bytes(2, "big") + ip[12:]
+        f = eth + b"\x08\x00" + ip + tcp
+    else:
+        length = len(tcp) if ip_length is None else int(ip_length)
+        f = eth + b"\x86\xdd" + b"\x60\x00\x00\x00" + length.to_bytes(2, "big") + b"\x06\x40" + src + dst + tcp
+    return f + bytes(max(0, pad_to - len(f)))
+
+
 # ---- TPACKET_V3 rings (linux/if_packet.h layouts) for the AF_PACKET ingest -------------
 TPV3_BLOCK_DESC = 48      # sizeof(struct tpacket_block_desc)
 TPV3_HDR = 48             # sizeof(struct tpacket3_hdr)
