@@ -3,8 +3,8 @@
 The product path is libgpd.so (HIP kernels for gfx950 behind the C-ABI in
 include/gpd.h); this package is the host-side mirror of gopacket's parser API
 (parser.py), its dispatch tables (layers.py), batch layout (batch.py), result
-reading (results.py), input formats (pcap.py, pcapng.py, afpacket.py, synth.py), the pcap
-writer and batch selection (pcapwrite.py), BPF filtering of a device batch (bpf.py), the flow
+reading (results.py), input formats (pcap.py, pcapng.py, afpacket.py, synth.py), the pcap and
+pcapng writers and batch selection (pcapwrite.py), BPF filtering of a device batch (bpf.py), the flow
 table (flows.py), the IPv4 fragment hand-off to ip4defrag (defrag.py) and the TCP segment
 hand-off to tcpassembly (tcpassembly.py).  (The stateful consumers of the two hand-offs are
 restated only as test checkers, oracle/ip4defrag_ref.py and tests/tcpassembly_ref.py: ip4defrag
@@ -29,4 +29,7 @@ def __getattr__(name):
     if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly"):
         import importlib
         return importlib.import_module("." + name, __name__)
+    if name in ("NgWriter", "NewNgWriter", "NewNgWriterInterface"):  # the pcapng writer (pcapwrite.py)
+        import importlib
+        return getattr(importlib.import_module(".pcapwrite", __name__), name)
     raise AttributeError(name)

@@ -5,6 +5,8 @@ record header and the packet's bytes on an io.Writer (pcapgo/write.go:101-129). 
 are a DeviceBatch in HBM and a mask says which to keep: gpd_pcap_write (include/gpd_pcapwrite.h)
 builds the stream on the device, a stream compaction over variable-length records, and
 gpd_batch_select repacks the same packets into a new dense batch for more work on the device.
+The pcapng form of the same way out is pcapgo.NgWriter (pcapgo/ngwrite.go): NgWriter below,
+over gpd_pcapng_write and the host-built blocks of include/gpd_pcapngwrite.h.
 
 The entry points are bound onto the loaded library here, on first use, from PW_EXPORTS: they
 live in their own header and are not part of _lib.EXPORTS.
@@ -14,7 +16,7 @@ from __future__ import annotations
 import ctypes as C
 import struct
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, field, replace
 from typing import Optional
 
 import numpy as np
@@ -22,6 +24,7 @@ import numpy as np
 from . import _lib
 from ._lib import GPD_ERR_INVALID, GPD_ERR_PCAP, GpdBatch, check
 from .pcap import PcapError
+from .pcapng import GpdPcapngIface, GpdPcapngSectionInfo, GpdPcapngStr, NgInterface, NgSectionInfo
 
 GPD_PCAPW_NANOS, GPD_PCAPW_FILE_HEADER = 1, 2
 NO_BAD_INDEX = 0xFFFFFFFFFFFFFFFF
@@ -60,6 +63,7 @@ class CaptureInfo:
     Timestamp: Optional[int] = None
     CaptureLength: int = 0
     Length: int = 0
+    InterfaceIndex: int = 0   # the NgWriter's (ngwrite.go:357-359); pcapgo.Writer does not look at it
 
 
 def file_header(snaplen: int, linktype: int, nanos: bool = False) -> bytes:
@@ -243,3 +247,238 @@ def select(parser_or_ctx, dbatch, keep, stream=None):
                                    _ptr(index), m, C.byref(k), C.byref(nb), C.c_void_p(s.cuda_stream)),
               "gpd_batch_select")
     return DeviceBatch.from_tensors(data, total, offset, caplen, dev), index
+
+
+# --- pcapng (pcapgo.NgWriter, pcapgo/ngwrite.go; include/gpd_pcapngwrite.h) ---------------------
+
+NgNoValue64 = 2 ** 64 - 1  # pcapng.go:120-121
+GPD_PCAPNGW_MAX_PREFIX = 65536
+BAD_NONE, BAD_IFACE, BAD_LENGTH = 0, 1, 2
+
+
+class GpdPcapngStats(C.Structure):
+    _fields_ = [("last_update", C.c_uint64), ("start_time", C.c_uint64), ("end_time", C.c_uint64),
+                ("packets_received", C.c_uint64), ("packets_dropped", C.c_uint64),
+                ("has_last_update", C.c_uint32), ("has_start_time", C.c_uint32),
+                ("has_end_time", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_BLOCK_TAIL = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]  # out, out_cap, *len
+NGW_EXPORTS = {
+    # include/gpd_pcapngwrite.h — name: (restype, argtypes)
+    "gpd_pcapng_section_block": (C.c_int, [C.POINTER(GpdPcapngSectionInfo), C.c_char_p, C.c_uint64] + _BLOCK_TAIL),
+    "gpd_pcapng_interface_block": (C.c_int, [C.POINTER(GpdPcapngIface), C.c_char_p, C.c_uint64] + _BLOCK_TAIL),
+    "gpd_pcapng_stats_block": (C.c_int, [C.c_int64, C.c_uint32, C.POINTER(GpdPcapngStats)] + _BLOCK_TAIL),
+    "gpd_pcapng_write": (C.c_int, [C.c_void_p, C.POINTER(GpdBatch), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint32), C.c_void_p]),
+}
+
+_ng_bound = False
+
+
+def ngw_lib():
+    """The loaded library with the pcapng writer's signatures bound (once)."""
+    global _ng_bound
+    if not _ng_bound:
+        for name, (res, args) in NGW_EXPORTS.items():
+            fn = getattr(_lib.lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _ng_bound = True
+    return _lib.lib
+
+
+@dataclass
+class NgWriterOptions:
+    """pcapgo.NgWriterOptions (ngwrite.go:22-25)."""
+    SectionInfo: NgSectionInfo = field(default_factory=NgSectionInfo)
+
+
+@dataclass
+class NgInterfaceStatistics:
+    """pcapgo.NgInterfaceStatistics (pcapng.go:123-136); a time is Unix ns, None Go's zero time."""
+    LastUpdate: Optional[int] = None
+    StartTime: Optional[int] = None
+    EndTime: Optional[int] = None
+    PacketsReceived: int = NgNoValue64
+    PacketsDropped: int = NgNoValue64
+
+
+# ngwrite.go:28-42, with what runtime.GOARCH / runtime.GOOS give on this platform
+DefaultNgWriterOptions = NgWriterOptions(NgSectionInfo(Hardware=b"amd64", OS=b"linux", Application=b"gopacket"))
+DefaultNgInterface = NgInterface(Name=b"intf0", OS=b"linux", SnapLength=0, TimestampResolution=9)
+
+
+def _strs(values):
+    """The strings back to back and their gpd_pcapng_str descriptors."""
+    descs, pos = [], 0
+    for v in values:
+        descs.append(GpdPcapngStr(pos, len(v), 0))
+        pos += len(v)
+    return b"".join(bytes(v) for v in values), descs
+
+
+def _built(fn, what, *args) -> bytes:
+    """A builder's block: the sizing call, then the block into a buffer of that size."""
+    n = C.c_uint64()
+    rc = fn(*args, None, 0, C.byref(n))
+    if rc == GPD_ERR_PCAP:
+        raise PcapError(_lib.lib.gpd_last_error_string().decode())
+    check(rc, what)
+    buf = (C.c_uint8 * max(1, n.value))()
+    check(fn(*args, buf, n.value, C.byref(n)), what)
+    return bytes(buf[:n.value])
+
+
+def ng_section_block(info: NgSectionInfo) -> bytes:
+    """writeSectionHeader's block (ngwrite.go:187-234), from gpd_pcapng_section_block."""
+    strs, d = _strs([info.Hardware, info.OS, info.Application, info.Comment])
+    c = GpdPcapngSectionInfo(d[0], d[1], d[2], d[3], int(info.big_endian), 0)
+    return _built(ngw_lib().gpd_pcapng_section_block, "gpd_pcapng_section_block", C.byref(c), strs, len(strs))
+
+
+def ng_interface_block(intf: NgInterface) -> bytes:
+    """AddInterface's block (ngwrite.go:237-298), from gpd_pcapng_interface_block."""
+    strs, d = _strs([intf.Name, intf.Comment, intf.Description, intf.Filter, intf.OS])
+    c = GpdPcapngIface(d[0], d[1], d[2], d[3], d[4], int(intf.TimestampOffset) & NgNoValue64, 0, 0, 0,
+                       int(intf.LinkType) & 0xFFFFFFFF, int(intf.SnapLength) & 0xFFFFFFFF,
+                       int(intf.TimestampResolution) & 0xFFFFFFFF, 0)
+    return _built(ngw_lib().gpd_pcapng_interface_block, "gpd_pcapng_interface_block", C.byref(c), strs, len(strs))
+
+
+def ng_stats_block(intf: int, n_ifaces: int, stats: NgInterfaceStatistics) -> bytes:
+    """WriteInterfaceStats's block (ngwrite.go:301-353), from gpd_pcapng_stats_block; PcapError
+    with the reference's text for an interface that was not added."""
+    t = lambda v: (0 if v is None else int(v) & NgNoValue64)
+    c = GpdPcapngStats(t(stats.LastUpdate), t(stats.StartTime), t(stats.EndTime),
+                       int(stats.PacketsReceived) & NgNoValue64, int(stats.PacketsDropped) & NgNoValue64,
+                       stats.LastUpdate is not None, stats.StartTime is not None, stats.EndTime is not None, 0)
+    return _built(ngw_lib().gpd_pcapng_stats_block, "gpd_pcapng_stats_block", int(intf), int(n_ifaces), C.byref(c))
+
+
+def _ng_write_call(h, dbatch, ts, wl, ifx, n_ifaces, kp, prefix, out, stream):
+    """One gpd_pcapng_write: (rc, records, bytes, bad index, bad reason); out None is the sizing call."""
+    nw, nb, bad, why = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+    b = dbatch.c_batch()
+    rc = ngw_lib().gpd_pcapng_write(h, C.byref(b), _ptr(ts), _ptr(wl), _ptr(ifx), n_ifaces, _ptr(kp),
+                                    prefix if prefix else None, len(prefix), _ptr(out),
+                                    out.numel() if out is not None else 0, C.byref(nw), C.byref(nb),
+                                    C.byref(bad), C.byref(why), C.c_void_p(stream.cuda_stream))
+    return rc, nw.value, nb.value, bad.value, why.value
+
+
+def write_device_ng(parser_or_ctx, dbatch, ts_ns, length=None, ifindex=None, n_ifaces: int = 1, keep=None,
+                    prefix: bytes = b"", stream=None, out=None):
+    """The kept packets of `dbatch` as enhanced packet blocks in HBM behind `prefix`
+    (gpd_pcapng_write): returns (uint8 device tensor trimmed to the stream, records written).
+    ts_ns (uint64, the bit pattern of Timestamp.UnixNano(), written raw), length
+    (CaptureInfo.Length; None: the capture length), ifindex (CaptureInfo.InterfaceIndex; None:
+    interface 0) and keep are torch device tensors or numpy arrays; n_ifaces is the number of
+    interfaces the stream has described so far; prefix the host bytes in front of the first record
+    (section and interface blocks).  Raises PcapError at the first kept packet on an interface
+    that was not added or with capture length > length; its .stream and .n_written hold what the
+    loop wrote before it, .bad_index the packet and .bad_reason which check (BAD_IFACE,
+    BAD_LENGTH)."""
+    from .parser import _torch
+    torch = _torch()
+    dev, n = dbatch.device, dbatch.n
+    h = _ctx_handle(parser_or_ctx)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    ts = _dev(ts_ns, np.uint64, dev, n, "ts_ns")
+    wl = _dev(length, np.uint32, dev, n, "length")
+    ifx = _dev(ifindex, np.uint32, dev, n, "ifindex")
+    kp = _keep_dev(keep, dev, n)
+    prefix = bytes(prefix)
+    args = (h, dbatch, ts, wl, ifx, int(n_ifaces), kp, prefix)
+    # without an `out` that fits, a sizing call first (the scan alone), then the write
+    rc, nw, nb, bad, why = _ng_write_call(*args, out, s)
+    if rc not in (0, GPD_ERR_PCAP) and not (rc == GPD_ERR_INVALID and out is not None and nb > out.numel()):
+        check(rc, "gpd_pcapng_write")
+    if out is None or nb > out.numel():
+        out = torch.empty(max(16, (nb + 15) & ~15), dtype=torch.uint8, device=torch.device("cuda", dev))
+        rc, nw, nb, bad, why = _ng_write_call(*args, out, s)
+    if rc == GPD_ERR_PCAP:
+        e = PcapError(_lib.lib.gpd_last_error_string().decode())
+        e.stream, e.n_written, e.bad_index, e.bad_reason = out[:nb], nw, bad, why
+        raise e
+    check(rc, "gpd_pcapng_write")
+    return out[:nb], nw
+
+
+class NgWriter:
+    """pcapgo.NgWriter (ngwrite.go:45-397) over any object with .write: the section header and
+    the first interface are written when it is made (NewNgWriterInterface, :66-79).  Written
+    streams are little-endian with the interfaces' timestamp resolution fixed to 9."""
+
+    def __init__(self, w, intf: NgInterface, options: NgWriterOptions):
+        self.w = w
+        self.options = options
+        self.intf = 0  # interfaces added so far
+        self.w.write(ng_section_block(options.SectionInfo))
+        self.AddInterface(intf)
+
+    def AddInterface(self, intf: NgInterface) -> int:
+        """ngwrite.go:237-298: returns the new interface's id."""
+        block = ng_interface_block(intf)
+        i, self.intf = self.intf, self.intf + 1
+        self.w.write(block)
+        return i
+
+    def WriteInterfaceStats(self, intf: int, stats: NgInterfaceStatistics) -> None:
+        """ngwrite.go:301-353."""
+        self.w.write(ng_stats_block(intf, self.intf, stats))
+
+    def WritePacket(self, ci, data: bytes) -> None:
+        """ngwrite.go:356-392 for one host packet.  The Timestamp is written as it is: the
+        interface's TimestampOffset is not subtracted (a reader adds it again)."""
+        if ci.InterfaceIndex >= self.intf or ci.InterfaceIndex < 0:
+            raise PcapError(f"Can't send statistics for non existent interface {ci.InterfaceIndex}; "
+                            f"have only {self.intf} interfaces")
+        if ci.CaptureLength != len(data):
+            raise PcapError(f"capture length {ci.CaptureLength} does not match data length {len(data)}")
+        if ci.CaptureLength > ci.Length:
+            raise PcapError(f"invalid capture info {ci!r}:  capture length > length")
+        pad = (4 - (len(data) & 3)) & 3
+        total = (len(data) + 32 + pad) & 0xFFFFFFFF
+        ts = (0 if ci.Timestamp is None else int(ci.Timestamp)) & NgNoValue64
+        self.w.write(struct.pack("<IIIIIII", 6, total, ci.InterfaceIndex, ts >> 32, ts & 0xFFFFFFFF,
+                                 ci.CaptureLength & 0xFFFFFFFF, ci.Length & 0xFFFFFFFF))
+        self.w.write(bytes(data))
+        self.w.write(bytes(pad) + struct.pack("<I", total))
+
+    def WritePackets(self, dbatch, ts_ns, length=None, ifindex=None, keep=None, parser=None) -> int:
+        """The WritePacket loop over the kept packets of a DeviceBatch, on the device
+        (gpd_pcapng_write); the records are copied back and written to w.  Returns the records
+        written.  At a rejected packet the records before it are written, then PcapError raised
+        with the reference's text, as the loop would have.  `parser` as for Writer.WritePackets."""
+        if parser is None:
+            parser = self._parser(dbatch.device)
+        try:
+            stream, nw = write_device_ng(parser, dbatch, ts_ns, length, ifindex, self.intf, keep)
+        except PcapError as e:
+            if getattr(e, "stream", None) is not None:
+                self.w.write(e.stream.cpu().numpy().tobytes())
+            raise
+        self.w.write(stream.cpu().numpy().tobytes())
+        return nw
+
+    _parser = Writer._parser
+
+    def Flush(self) -> None:
+        """ngwrite.go:395-397: passes the flush on when w has one (nothing is buffered here)."""
+        flush = getattr(self.w, "flush", None)
+        if flush is not None:
+            flush()
+
+
+def NewNgWriterInterface(w, intf: NgInterface, options: NgWriterOptions) -> NgWriter:
+    """pcapgo.NewNgWriterInterface (ngwrite.go:66-79)."""
+    return NgWriter(w, intf, options)
+
+
+def NewNgWriter(w, linktype: int) -> NgWriter:
+    """pcapgo.NewNgWriter (ngwrite.go:56-60): DefaultNgInterface with the link type, and
+    DefaultNgWriterOptions."""
+    return NgWriter(w, replace(DefaultNgInterface, LinkType=int(linktype)), DefaultNgWriterOptions)

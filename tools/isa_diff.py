@@ -1,4 +1,5 @@
-"""Compare the decode kernels' device code between two source trees, kernel by kernel:
+"""Compare the decode kernels' and the pcap writer's device code between two source trees, kernel
+by kernel:
     python tools/isa_diff.py OLD_TREE NEW_TREE [--diag] [-DFLAG ...]
 Each tree's kernel translation units (whichever of KERNEL_TUS it has) are compiled to gfx950
 assembly and every kernel's instruction stream is compared after dropping comments and assembler
@@ -16,7 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFILT = os.environ.get("CXXFILT", "c++filt")
-KERNEL_TUS = ["gpd_kernels.hip", "gpd_rs.hip", "gpd_ro.hip", "gpd_sp.hip"]
+KERNEL_TUS = ["gpd_kernels.hip", "gpd_rs.hip", "gpd_ro.hip", "gpd_sp.hip", "gpd_pcapwrite.hip"]
 
 
 def kernel_tus(tree):
@@ -62,7 +63,7 @@ def key(demangled):
         a = [x.strip() for x in m.group(1).split(",")]
         stage, ext, pages = (a[0], a[2], a[3]) if len(a) == 9 else a
         return f"gpd::decode_kernel<STAGE={stage}, EXT={ext}, PAGES={pages}>"
-    return re.sub(r"^void ", "", demangled).split("(")[0]
+    return re.sub(r"^void ", "", demangled.replace("(anonymous namespace)::", "")).split("(")[0]
 
 
 def keyed(kernels):
