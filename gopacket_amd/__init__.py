@@ -6,9 +6,10 @@ include/gpd.h); this package is the host-side mirror of gopacket's parser API
 reading (results.py), input formats (pcap.py, pcapng.py, afpacket.py, synth.py), the pcap and
 pcapng writers and batch selection (pcapwrite.py), BPF filtering of a device batch (bpf.py), the flow
 table (flows.py), the IPv4 fragment hand-off to ip4defrag (defrag.py) and the TCP segment
-hand-off to tcpassembly (tcpassembly.py).  (The stateful consumers of the two hand-offs are
-restated only as test checkers, oracle/ip4defrag_ref.py and tests/tcpassembly_ref.py: ip4defrag
-and the stream assembler themselves are out of scope.)
+hand-off to tcpassembly (tcpassembly.py) and the stream assembly over it (tcpstream.py: the
+Reassembly lists per connection, built on the device).  (ip4defrag, the stateful consumer of the
+fragment hand-off, is restated only as a test checker, oracle/ip4defrag_ref.py; the stream
+assembler's restatement tests/tcpassembly_ref.py is the oracle of tcpstream.py.)
 """
 from . import layers
 from .layers import *  # noqa: F401,F403  LayerType constants, Register*PortLayerType
@@ -19,14 +20,14 @@ from .results import (BatchResult, Endpoint, FastHashes, Flow, FlowFromEndpoints
 
 __all__ = ["layers", "PacketBatch", "BatchResult", "DecodeError", "UnsupportedLayerType",
            "Endpoint", "Flow", "NewEndpoint", "NewFlow", "FlowFromEndpoints", "FastHashes",
-           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly"]
+           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream"]
 
 
 def __getattr__(name):
     # the parser pulls in libgpd.so; import it lazily so that pure-host helpers
     # (pcap, synth, layers) work in environments that only build.
-    # (pcapng, pcapwrite, bpf and tcpassembly bind their entry points onto libgpd.so too)
-    if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly"):
+    # (pcapng, pcapwrite, bpf, tcpassembly and tcpstream bind their entry points onto libgpd.so too)
+    if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("NgWriter", "NewNgWriter", "NewNgWriterInterface"):  # the pcapng writer (pcapwrite.py)

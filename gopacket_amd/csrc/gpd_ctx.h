@@ -152,7 +152,7 @@ struct gpd_ctx {
   struct Scratch {
     void *d = nullptr;
     size_t bytes = 0;
-  } scratch[17];
+  } scratch[18];
   gpd_tuning tune{0, -1, -1, 0, -1, -1, 0, -1};  // gpd_ctx_set_tuning (all automatic by default)
   bool timing = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr;

@@ -1,0 +1,556 @@
+// gpd_tcpstream.hip — TCP stream assembly (include/gpd_tcpstream.h): the Reassembly lists
+// tcpassembly's Assembler hands to its streams (tcpassembly/assembly.go:533-607, the drain
+// :235-266,645-657 and FlushAll :276-287), built from the grouped segment hand-off
+// (gpd_tcpseg.hip) with one wave per connection, and the records' bytes gathered into
+// per-connection streams.
+//
+// Launches, separated by launch boundaries only (no kernel waits on another workgroup):
+//
+//   ta_pages_sum_kernel   per 2,048 segments: the pages they would be buffered in,
+//                         max(1, ceil(payload_len / 1900)) each
+//   ta_scan_kernel        one workgroup: exclusive scan of the block sums (gpd_compact.h)
+//   ta_pages_apply_kernel the exclusive scan per segment: a segment's first page id, and with it
+//                         a group's private record region (a page or a segment yields one record
+//                         at most, so a group's pages bound its records)
+//   ta_walk_kernel        one wave per group: the assembler's state machine
+//                         (gpd_tcpstream_walk.h) on lane 0, the in-order run on all 64 lanes;
+//                         records into the private region, totals per group
+//   ta_group_sum / scan / apply   the groups' record, byte and call counts scanned (three arrays at
+//                         once; the calls only for their total: a million waves adding to one
+//                         word would queue up behind each other)
+//   ta_totals_kernel      out[] for the host, which decides here whether anything is written
+//   ta_place_kernel       one wave per group: its records to their dense places with the final
+//                         stream_off, its stream record, its connection state
+//   ta_gather_kernel      the bandwidth path: a wave per 64 consecutive records, whose bytes are
+//                         one contiguous run of the output, in 16-byte-aligned output chunks
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "gpd_compact.h"
+#include "gpd_internal.h"
+#include "gpd_tcpstream_walk.h"
+
+namespace gpd {
+namespace {
+
+static_assert(sizeof(gpd_tcp_conn) == 8 && sizeof(gpd_tcp_asm_opts) == 8 && sizeof(gpd_tcp_reasm) == 32 &&
+                  sizeof(gpd_tcp_stream) == 48 && sizeof(TsmNode) == 32,
+              "include/gpd_tcpstream.h layouts");
+
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+constexpr uint32_t kWalkWaves = 4;    // waves (groups) per walk / place workgroup
+constexpr uint32_t kGatherWaves = 4;  // waves per gather workgroup
+
+struct TaArgs {
+  const uint8_t *data;
+  uint64_t dlen, lim;  // lim: data_len rounded up to 16, the end of what a 16-byte load may touch
+  const uint32_t *offset;
+  uint32_t n;
+  const gpd_tcp_seg *segs;
+  uint32_t cnt;
+  const gpd_tcp_group *groups;
+  uint32_t ng;
+  gpd_tcp_conn *state;
+  uint32_t id_bound;
+  uint32_t max_pages, close_all;
+  gpd_tcp_reasm *recs;  // the caller's
+  gpd_tcp_stream *streams;
+  uint8_t *bytes;
+  uint32_t nrecs;       // known on the host after the totals
+  uint64_t nbytes;
+  // scratch of the context
+  uint64_t *res;        // [0..3] out[], [4] pages in all (the one atomic: a word per 2,048 segments)
+  uint32_t *pbase;      // cnt + 1: a segment's first page id
+  uint32_t *blk;        // block sums of the scan in flight: (nblk + 1) words per array
+  uint32_t nblk;
+  uint32_t *gsc;        // [3][ng]: records, bytes and calls per group -> their exclusive scans
+  gpd_tcp_stream *sstr; // ng: the stream records before their places are known
+  TsmNode *nodes;       // one per page
+  gpd_tcp_reasm *precs; // one per page: the groups' private record regions
+};
+
+// ---- the two-level scan: block sums, compact_scan over them, the prefix per item -----------------
+// Called by the 256 lanes of workgroup blockIdx.x.  total64 (may be NULL) gets the exact sum.
+template <class F>
+__device__ __forceinline__ void scan_sum(uint32_t n, uint32_t *blk, uint64_t *total64, F val) {
+  __shared__ uint64_t wsum[4];
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t base = blockIdx.x * kCompactBlock;
+  uint64_t c = 0;
+  for (uint32_t r = 0; r < kCompactBlock / 256u; ++r) {
+    const uint32_t i = base + r * 256u + threadIdx.x;
+    if (i < n) c += val(i);
+  }
+#pragma unroll
+  for (uint32_t d = 32; d >= 1u; d >>= 1) {
+    const uint32_t lo = __shfl_xor((uint32_t)c, d, 64), hi = __shfl_xor((uint32_t)(c >> 32), d, 64);
+    c += ((uint64_t)hi << 32) | lo;
+  }
+  if (lane == 0) wsum[w] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint64_t s = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    blk[blockIdx.x] = s > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)s;
+    if (total64) atomicAdd(reinterpret_cast<unsigned long long *>(total64), (unsigned long long)s);
+  }
+}
+
+// out[i] = the sum of val over the items before i; with_total: out[n] = the sum of all.  out may
+// be the array val reads (a lane reads its item before it writes it).
+template <class F>
+__device__ __forceinline__ void scan_apply(uint32_t n, const uint32_t *blk, uint32_t *out, bool with_total, F val) {
+  __shared__ uint32_t ws[4];
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t base = blockIdx.x * kCompactBlock;
+  uint32_t carry = blk[blockIdx.x];
+  for (uint32_t r = 0; r < kCompactBlock / 256u; ++r) {
+    const uint32_t i = base + r * 256u + threadIdx.x;
+    const uint32_t v = i < n ? val(i) : 0u;
+    const uint32_t x = wave_scan32(v, lane);
+    if (lane == 63u) ws[w] = x;
+    __syncthreads();
+    uint32_t before = carry;
+    for (uint32_t j = 0; j < w; ++j) before += ws[j];
+    if (i < n) out[i] = before + x - v;
+    if (with_total && i + 1u == n) out[n] = before + x;
+    carry += ws[0] + ws[1] + ws[2] + ws[3];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void ta_pages_sum_kernel(TaArgs A) {
+  scan_sum(A.cnt, A.blk, A.res + 4, [&A](uint32_t i) { return tsm_pages(A.segs[i].payload_len); });
+}
+__global__ __launch_bounds__(256) void ta_pages_apply_kernel(TaArgs A) {
+  scan_apply(A.cnt, A.blk, A.pbase, true, [&A](uint32_t i) { return tsm_pages(A.segs[i].payload_len); });
+}
+// blockIdx.y: the array (0 records, 1 bytes, 2 calls)
+__global__ __launch_bounds__(256) void ta_group_sum_kernel(TaArgs A) {
+  const uint32_t *v = A.gsc + (size_t)blockIdx.y * A.ng;
+  scan_sum(A.ng, A.blk + (size_t)blockIdx.y * (A.nblk + 1u), nullptr, [v](uint32_t i) { return v[i]; });
+}
+__global__ __launch_bounds__(256) void ta_group_apply_kernel(TaArgs A) {
+  uint32_t *v = A.gsc + (size_t)blockIdx.y * A.ng;
+  scan_apply(A.ng, A.blk + (size_t)blockIdx.y * (A.nblk + 1u), v, false, [v](uint32_t i) { return v[i]; });
+}
+__global__ __launch_bounds__(1024) void ta_scan_kernel(TaArgs A) {
+  compact_scan(A.blk + (size_t)blockIdx.x * (A.nblk + 1u), A.nblk);
+}
+
+// ---- the walk ---------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t first_lane(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ void conn_from_lane0(TsmConn &c) {  // (lane 0 is the wave's first lane)
+  c.exists = first_lane(c.exists);
+  c.valid = first_lane(c.valid);
+  c.next_seq = first_lane(c.next_seq);
+  c.first = first_lane(c.first);
+  c.last = first_lane(c.last);
+  c.pages = first_lane(c.pages);
+  c.nrec = first_lane(c.nrec);
+  c.ncalls = first_lane(c.ncalls);
+  c.completed = first_lane(c.completed);
+  c.nbytes = first_lane(c.nbytes);
+}
+
+__device__ __forceinline__ gpd_tcp_seg load_seg(const gpd_tcp_seg *p) {
+  gpd_tcp_seg s;
+  const uint4 *q = reinterpret_cast<const uint4 *>(p);
+  uint4 *d = reinterpret_cast<uint4 *>(&s);
+  d[0] = q[0];
+  d[1] = q[1];
+  return s;
+}
+
+// The group's segments clamped to segs[] (the arrays are the caller's).
+__device__ __forceinline__ void group_range(const TaArgs &A, const gpd_tcp_group &G, uint32_t &start, uint32_t &count) {
+  start = min(G.start, A.cnt);
+  count = min(G.count, A.cnt - start);
+}
+
+// One wave per group.  The sequential step runs on lane 0.  On top of it the wave takes the
+// in-order run: with the connection open, nextSeq known and no page buffered, the following
+// segments (up to 64) whose seq is nextSeq plus the payload bytes before them in the run, and that
+// carry neither FIN nor RST, are each what :591-602 makes of them: one call, one record, skip 0,
+// no flags, the whole payload.  The first segment that breaks the chain takes the step.
+__global__ __launch_bounds__(64 * kWalkWaves) void ta_walk_kernel(TaArgs A) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t g = blockIdx.x * kWalkWaves + (threadIdx.x >> 6);
+  if (g >= A.ng) return;
+  const gpd_tcp_group G = A.groups[g];
+  uint32_t start, count;
+  group_range(A, G, start, count);
+  const bool un = G.flow_id == GPD_TCP_UNGROUPED;
+  uint32_t open = 0, ns = 0;
+  if (!un && A.state && G.flow_id < A.id_bound) {
+    const gpd_tcp_conn s = A.state[G.flow_id];
+    open = s.flags & GPD_TCP_CONN_OPEN;
+    ns = open ? s.next_seq : 0u;
+  }
+  TsmConn c;
+  tsm_conn_init(c, open, ns);
+  const uint32_t p0 = A.pbase[start];
+  const TsmIo io{A.nodes, A.precs + p0, A.pbase[start + count] - p0, A.max_pages};
+  if (!un) {
+    uint32_t i = 0;
+    while (i < count) {
+#ifndef GPD_TSM_NO_CHAIN  // (A/B: tools/tcpstream_time.py)
+      if (c.exists && c.valid && c.first == kTsmNil) {
+        const uint32_t j = i + lane;
+        const bool in = j < count;
+        gpd_tcp_seg s{};
+        if (in) s = load_seg(A.segs + start + j);
+        const uint32_t len = in ? s.payload_len : 0u;
+        const uint32_t incl = wave_scan32(len, lane), excl = incl - len;
+        const bool ok = in && s.seq == c.next_seq + excl && !(s.flags & (GPD_TCP_FIN | GPD_TCP_RST)) &&
+                        (len > 0u || (s.flags & GPD_TCP_SYN));
+        const uint64_t m = __ballot(ok);
+        const uint32_t run = m == ~0ull ? 64u : (uint32_t)__builtin_ctzll(~m);
+        if (run) {
+          if (lane < run && c.nrec + lane < io.cap) {
+            const v4u r0{s.packet, len ? s.payload_off : 0u, len, 0u};
+            const v4u r1{c.nbytes + excl, 0u, c.ncalls + lane, 0u};
+            v4u *d = reinterpret_cast<v4u *>(io.recs + c.nrec + lane);
+            d[0] = r0;
+            d[1] = r1;
+          }
+          const uint32_t total = __shfl(incl, (int)run - 1, 64);
+          c.nrec += run;
+          c.ncalls += run;
+          c.nbytes += total;
+          c.next_seq += total;
+          i += run;
+          continue;
+        }
+      }
+#endif
+      if (lane == 0) {
+        const gpd_tcp_seg s = load_seg(A.segs + start + i);
+        tsm_step(c, io, s, A.pbase[start + i]);
+      }
+      conn_from_lane0(c);
+      ++i;
+    }
+    if (lane == 0) tsm_finish(c, io, A.close_all != 0);
+  }
+  if (lane == 0) {
+    A.gsc[g] = un ? 0u : c.nrec;
+    A.gsc[(size_t)A.ng + g] = un ? 0u : c.nbytes;
+    A.gsc[2 * (size_t)A.ng + g] = un ? 0u : c.ncalls;
+    gpd_tcp_stream S{};
+    S.flow_id = G.flow_id;
+    S.nrec = c.nrec;
+    S.ncalls = c.ncalls;
+    S.nbytes = c.nbytes;
+    S.completed = c.completed;
+    S.open = c.exists;
+    S.next_seq = c.exists ? c.next_seq : 0u;
+    A.sstr[g] = S;
+  }
+}
+
+__global__ __launch_bounds__(64) void ta_totals_kernel(TaArgs A) {
+  if (threadIdx.x != 0) return;
+  A.res[0] = A.blk[A.nblk];
+  A.res[1] = A.ng - (A.groups[A.ng - 1u].flow_id == GPD_TCP_UNGROUPED ? 1u : 0u);
+  A.res[2] = A.blk[(size_t)(A.nblk + 1u) + A.nblk];
+  A.res[3] = A.blk[2 * (size_t)(A.nblk + 1u) + A.nblk];
+}
+
+// One wave per group: the private records to recs[first_rec ...] with the stream's byte offset
+// added, the stream record, the connection's state.
+__global__ __launch_bounds__(64 * kWalkWaves) void ta_place_kernel(TaArgs A) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t g = blockIdx.x * kWalkWaves + (threadIdx.x >> 6);
+  if (g >= A.ng) return;
+  const gpd_tcp_group G = A.groups[g];
+  if (G.flow_id == GPD_TCP_UNGROUPED) return;
+  uint32_t start, count;
+  group_range(A, G, start, count);
+  gpd_tcp_stream S = A.sstr[g];
+  const uint32_t fr = A.gsc[g], bo = A.gsc[(size_t)A.ng + g];
+  const v4u *src = reinterpret_cast<const v4u *>(A.precs + A.pbase[start]);
+  v4u *dst = reinterpret_cast<v4u *>(A.recs + fr);
+  for (uint32_t r = lane; r < S.nrec; r += 64u) {
+    const v4u a = src[2u * r];
+    v4u b = src[2u * r + 1u];
+    const uint64_t so = (((uint64_t)b.y << 32) | b.x) + bo;
+    b.x = (uint32_t)so;
+    b.y = (uint32_t)(so >> 32);
+    dst[2u * r] = a;
+    dst[2u * r + 1u] = b;
+  }
+  if (lane == 0) {
+    S.first_rec = fr;
+    S.byte_off = bo;
+    const v4u *s4 = reinterpret_cast<const v4u *>(&S);
+    v4u *d4 = reinterpret_cast<v4u *>(A.streams + g);
+    d4[0] = s4[0];
+    d4[1] = s4[1];
+    d4[2] = s4[2];
+    if (A.state && G.flow_id < A.id_bound) A.state[G.flow_id] = gpd_tcp_conn{S.next_seq, S.open ? GPD_TCP_CONN_OPEN : 0u};
+  }
+}
+
+// ---- the gather, 16 bytes at a time -------------------------------------------------------------
+// bytes [s, s + 16) of the 32 bytes lo:hi, s in 0..15
+__device__ inline v4u bytes_from(v4u lo, v4u hi, uint32_t s) {
+  uint32_t x0 = lo.x, x1 = lo.y, x2 = lo.z, x3 = lo.w, x4 = hi.x, x5 = hi.y, x6 = hi.z, x7 = hi.w;
+  if (s & 8u) {
+    x0 = x2, x1 = x3, x2 = x4, x3 = x5, x4 = x6, x5 = x7;
+  }
+  if (s & 4u) {
+    x0 = x1, x1 = x2, x2 = x3, x3 = x4, x4 = x5;
+  }
+  const uint32_t b = (s & 3u) * 8u;
+  return v4u{__funnelshift_r(x0, x1, b), __funnelshift_r(x1, x2, b), __funnelshift_r(x2, x3, b),
+             __funnelshift_r(x3, x4, b)};
+}
+__device__ inline uint32_t low_bytes(int32_t k) {  // 0xFF in the k lowest bytes (k clamped to 0..4)
+  return k <= 0 ? 0u : k >= 4 ? 0xFFFFFFFFu : (1u << (8 * k)) - 1u;
+}
+// 0xFF in bytes [k0, k1) of 16
+__device__ inline v4u byte_mask(int32_t k0, int32_t k1) {
+  return v4u{low_bytes(k1) & ~low_bytes(k0), low_bytes(k1 - 4) & ~low_bytes(k0 - 4),
+             low_bytes(k1 - 8) & ~low_bytes(k0 - 8), low_bytes(k1 - 12) & ~low_bytes(k0 - 12)};
+}
+// data[a, a + 16) for a signed byte position, from two aligned 16-byte loads shifted together;
+// bytes no load may fetch (outside [0, lim)) read as zero (the callers mask them away)
+__device__ inline v4u src16(const TaArgs &A, int64_t a) {
+  const int64_t a0 = a & ~(int64_t)15;
+  const uint32_t s = (uint32_t)(a & 15);
+  const v4u z{0u, 0u, 0u, 0u};
+  const v4u lo = (a0 >= 0 && (uint64_t)a0 < A.lim) ? *reinterpret_cast<const v4u *>(A.data + a0) : z;
+  const v4u hi = (s != 0u && a0 + 16 >= 0 && (uint64_t)(a0 + 16) < A.lim) ? *reinterpret_cast<const v4u *>(A.data + a0 + 16) : z;
+  return bytes_from(lo, hi, s);
+}
+
+struct GRec {    // a wave's record as the chunks see it (LDS, 24 bytes)
+  uint64_t pos;  // where its bytes start in the output
+  int64_t src;   // where they start in the batch's data
+  uint32_t len, pad;
+};
+constexpr int64_t kNoSrc = (int64_t)1 << 62;  // a record whose packet is not the batch's: zeros
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
+  const uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// A wave per 64 consecutive records; their bytes are the contiguous run [P0, P1) of the output.
+// The wave owns the 16-byte output chunks that start inside its run.  A chunk is assembled in
+// registers from the records it covers — one record for all but the chunks at record borders —
+// each piece two aligned 16-byte source loads shifted together and masked, and leaves as one
+// 16-byte store.  Records can be 0 to 15 bytes long, so the run's last chunk may reach into any
+// number of later waves' records: that chunk, and the stream's ragged end, go byte by byte.
+__global__ __launch_bounds__(64 * kGatherWaves) void ta_gather_kernel(TaArgs A) {
+  __shared__ GRec s_rec[kGatherWaves][64];
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint64_t r0 = ((uint64_t)blockIdx.x * kGatherWaves + w) * 64u;
+  const bool wlive = r0 < A.nrecs;
+  const uint64_t ri = r0 + lane;
+  const bool live = ri < A.nrecs;
+  GRec q{~0ull, kNoSrc, 0u, 0u};
+  if (live) {
+    const v4u *p = reinterpret_cast<const v4u *>(A.recs + ri);
+    const v4u a = p[0], b = p[1];  // packet, src_off, len, skip | stream_off, call, flags
+    q.pos = ((uint64_t)b.y << 32) | b.x;
+    q.len = a.z;
+    if (a.x < A.n) q.src = (int64_t)A.offset[a.x] + (int64_t)a.y;
+  }
+  s_rec[w][lane] = q;
+  __syncthreads();
+  if (!wlive) return;
+  const uint32_t nl = A.nrecs - r0 < 64ull ? (uint32_t)(A.nrecs - r0) : 64u;
+  const uint64_t P0 = shfl64(q.pos, 0), P1 = shfl64(q.pos + q.len, (int)nl - 1);
+  const GRec *rec = s_rec[w];
+  const uint64_t c_lo = (P0 + 15ull) >> 4, c_hi = (P1 + 15ull) >> 4;
+  const v4u z{0u, 0u, 0u, 0u};
+  for (uint64_t c = c_lo + lane; c < c_hi; c += 64ull) {
+    const uint64_t cb = c << 4, ce = cb + 16ull;
+    if (ce > P1 && P1 < A.nbytes) {  // reaches into later waves' records: byte by byte
+      const uint64_t end = ce < A.nbytes ? ce : A.nbytes;
+      uint32_t lo = 0;
+#pragma unroll
+      for (uint32_t step = 32; step >= 1u; step >>= 1)
+        if (rec[lo + step].pos <= cb) lo += step;
+      uint64_t k = r0 + lo, x = cb;
+      while (x < end && k < A.nrecs) {
+        const gpd_tcp_reasm R = A.recs[k];
+        if (R.stream_off > x) break;  // (cannot happen: the records' bytes are back to back)
+        if (R.stream_off + R.len <= x) {
+          ++k;
+          continue;
+        }
+        const uint64_t sa = R.packet < A.n ? (uint64_t)A.offset[R.packet] + R.src_off + (x - R.stream_off) : ~0ull;
+        A.bytes[x] = sa < A.dlen ? A.data[sa] : (uint8_t)0;
+        ++x;
+      }
+      continue;
+    }
+    const uint64_t end = ce < P1 ? ce : P1;  // (end < ce: P1 == nbytes, the stream's ragged end)
+    v4u V = z;
+    uint64_t x = cb;
+    while (x < end) {
+      uint32_t lo = 0;  // the last record with pos <= x: the one x lies in
+#pragma unroll
+      for (uint32_t step = 32; step >= 1u; step >>= 1)
+        if (rec[lo + step].pos <= x) lo += step;
+      const GRec t = rec[lo];
+      const uint64_t qe = t.pos + t.len;
+      if (qe <= x) break;  // (cannot happen: x < P1)
+      const uint64_t pe = qe < end ? qe : end;
+      const int32_t k0 = (int32_t)(x - cb), k1 = (int32_t)(pe - cb);
+      V |= src16(A, t.src + (int64_t)(x - t.pos) - k0) & byte_mask(k0, k1);
+      x = pe;
+    }
+    if (end == ce) {
+      __builtin_nontemporal_store(V, reinterpret_cast<v4u *>(A.bytes + cb));
+    } else {
+      const uint32_t wds[4] = {V.x, V.y, V.z, V.w};
+      const uint32_t vend = (uint32_t)(end - cb);
+#pragma unroll
+      for (uint32_t b = 0; b < 16u; ++b)
+        if (b < vend) A.bytes[cb + b] = (uint8_t)(wds[b >> 2] >> ((b & 3u) * 8u));
+    }
+  }
+}
+
+#define TA_TRY(expr)                                                                        \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
+  } while (0)
+
+inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+
+}  // namespace
+}  // namespace gpd
+
+extern "C" int gpd_tcp_assemble(gpd_ctx *ctx, const gpd_batch *in, const gpd_tcp_seg *segs, uint64_t count,
+                                const gpd_tcp_group *groups, uint64_t ngroups, gpd_tcp_conn *state,
+                                uint32_t id_bound, const gpd_tcp_asm_opts *opts, gpd_tcp_reasm *recs,
+                                uint64_t max_recs, gpd_tcp_stream *streams, uint8_t *bytes, uint64_t max_bytes,
+                                uint64_t out[4], void *stream) {
+  using namespace gpd;
+  const char *who = "gpd_tcp_assemble";
+  if (!ctx || !in || !opts || !out) return set_error(GPD_ERR_INVALID, "%s: null argument", who);
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (in->n > 0xFFFFFF00ull)
+    return set_error(GPD_ERR_INVALID, "%s: batch of %llu packets (max 2^32 - 256)", who, (unsigned long long)in->n);
+  if (count >= 0x80000000ull)
+    return set_error(GPD_ERR_INVALID, "%s: %llu segments (max 2^31 - 1)", who, (unsigned long long)count);
+  if (ngroups > count)
+    return set_error(GPD_ERR_INVALID, "%s: %llu groups of %llu segments", who, (unsigned long long)ngroups,
+                     (unsigned long long)count);
+  if (max_recs && !recs) return set_error(GPD_ERR_INVALID, "%s: null recs with max_recs > 0", who);
+  if (max_bytes && !bytes) return set_error(GPD_ERR_INVALID, "%s: null bytes with max_bytes > 0", who);
+  if (bytes && !recs) return set_error(GPD_ERR_INVALID, "%s: bytes without recs", who);
+  if (recs && !streams) return set_error(GPD_ERR_INVALID, "%s: recs without streams[]", who);
+  if (((uintptr_t)recs & 15u) || ((uintptr_t)streams & 15u) || ((uintptr_t)bytes & 15u))
+    return set_error(GPD_ERR_INVALID, "%s: recs, streams and bytes must be 16-byte aligned", who);
+  if (((uintptr_t)segs & 15u) || ((uintptr_t)groups & 15u))
+    return set_error(GPD_ERR_INVALID, "%s: segs and groups must be 16-byte aligned", who);
+  if (count == 0 || ngroups == 0) return GPD_OK;
+  if (!segs || !groups) return set_error(GPD_ERR_INVALID, "%s: null segs or groups", who);
+  if (!in->data || !in->offset || !in->caplen)
+    return set_error(GPD_ERR_INVALID, "%s: batch data/offset/caplen must be non-NULL", who);
+  if (in->data_len >= 0xFFFFFFF0ull)
+    return set_error(GPD_ERR_INVALID, "%s: data_len %llu outside the 32-bit offset range", who,
+                     (unsigned long long)in->data_len);
+  DeviceScope dscope_;
+  TA_TRY(dscope_.set(ctx_device(ctx)));
+  const hipStream_t s = (hipStream_t)stream;
+  TaArgs A{};
+  A.data = in->data;
+  A.dlen = in->data_len;
+  A.lim = (in->data_len + 15ull) & ~15ull;
+  A.offset = in->offset;
+  A.n = (uint32_t)in->n;
+  A.segs = segs;
+  A.cnt = (uint32_t)count;
+  A.groups = groups;
+  A.ng = (uint32_t)ngroups;
+  A.state = state;
+  A.id_bound = state ? id_bound : 0u;
+  A.max_pages = opts->max_pages_per_connection;
+  A.close_all = opts->close_all;
+  A.recs = recs;
+  A.streams = streams;
+  A.bytes = bytes;
+  // scratch sized by the hand-off: result words, page ids, block sums, the groups' counts and streams
+  const uint32_t nblk_s = (A.cnt + kCompactBlock - 1u) / kCompactBlock;
+  const uint32_t nblk_g = (A.ng + kCompactBlock - 1u) / kCompactBlock;
+  const size_t b_res = 64, b_pbase = up16(((size_t)A.cnt + 1) * 4);
+  const size_t b_blk = up16(3 * ((size_t)std::max(nblk_s, nblk_g) + 1) * 4);
+  const size_t b_gsc = up16(3 * (size_t)A.ng * 4), b_sstr = (size_t)A.ng * sizeof(gpd_tcp_stream);
+  const size_t fixed = b_res + b_pbase + b_blk + b_gsc + b_sstr;
+  // One slot holds the page arrays behind the fixed part; it grows once the pages are counted.
+  // The first guess (one page per segment) is right for every payload up to 1900 bytes.
+  auto carve = [&](uint8_t *base) {
+    A.res = reinterpret_cast<uint64_t *>(base);
+    A.pbase = reinterpret_cast<uint32_t *>(base + b_res);
+    A.blk = reinterpret_cast<uint32_t *>(base + b_res + b_pbase);
+    A.gsc = reinterpret_cast<uint32_t *>(base + b_res + b_pbase + b_blk);
+    A.sstr = reinterpret_cast<gpd_tcp_stream *>(base + b_res + b_pbase + b_blk + b_gsc);
+  };
+  auto *base = static_cast<uint8_t *>(ctx_scratch(ctx, 17, fixed + 2 * (size_t)A.cnt * sizeof(TsmNode)));
+  if (!base) return set_error(GPD_ERR_NOMEM, "%s: scratch allocation failed", who);
+  carve(base);
+  A.nblk = nblk_s;
+  TA_TRY(hipMemsetAsync(A.res, 0, b_res, s));
+  hipLaunchKernelGGL(ta_pages_sum_kernel, dim3(nblk_s), dim3(256), 0, s, A);
+  TA_TRY(hipGetLastError());
+  uint64_t npages = 0;
+  TA_TRY(hipMemcpyAsync(&npages, A.res + 4, 8, hipMemcpyDeviceToHost, s));
+  TA_TRY(hipStreamSynchronize(s));
+  if (npages > 0xFFFFFFFFull)
+    return set_error(GPD_ERR_INVALID, "%s: %llu pages (max 2^32 - 1)", who, (unsigned long long)npages);
+  // the page arrays: nodes and private records, 32 bytes each per page.  Growing the slot
+  // replaces it; all it held so far is the block sums, which are computed again.
+  const size_t b_pages = (size_t)npages * sizeof(TsmNode);
+  if (npages > A.cnt) {
+    base = static_cast<uint8_t *>(ctx_scratch(ctx, 17, fixed + 2 * b_pages));
+    if (!base) return set_error(GPD_ERR_NOMEM, "%s: scratch allocation failed", who);
+    carve(base);
+    TA_TRY(hipMemsetAsync(A.res, 0, b_res, s));
+    hipLaunchKernelGGL(ta_pages_sum_kernel, dim3(nblk_s), dim3(256), 0, s, A);
+  }
+  A.nodes = reinterpret_cast<TsmNode *>(base + fixed);
+  A.precs = reinterpret_cast<gpd_tcp_reasm *>(base + fixed + b_pages);
+  hipLaunchKernelGGL(ta_scan_kernel, dim3(1), dim3(1024), 0, s, A);
+  hipLaunchKernelGGL(ta_pages_apply_kernel, dim3(nblk_s), dim3(256), 0, s, A);
+  const unsigned wgrid = (A.ng + kWalkWaves - 1u) / kWalkWaves;
+  hipLaunchKernelGGL(ta_walk_kernel, dim3(wgrid), dim3(64 * kWalkWaves), 0, s, A);
+  A.nblk = nblk_g;
+  hipLaunchKernelGGL(ta_group_sum_kernel, dim3(nblk_g, 3), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(ta_scan_kernel, dim3(3), dim3(1024), 0, s, A);
+  hipLaunchKernelGGL(ta_group_apply_kernel, dim3(nblk_g, 2), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(ta_totals_kernel, dim3(1), dim3(64), 0, s, A);
+  TA_TRY(hipGetLastError());
+  uint64_t tot[4] = {0, 0, 0, 0};
+  TA_TRY(hipMemcpyAsync(tot, A.res, 32, hipMemcpyDeviceToHost, s));
+  TA_TRY(hipStreamSynchronize(s));
+  for (int k = 0; k < 4; ++k) out[k] = tot[k];
+  if (!recs && !max_recs) return GPD_OK;  // the sizing call
+  const bool gather = bytes != nullptr || max_bytes != 0;
+  if (tot[0] > max_recs)
+    return set_error(GPD_ERR_INVALID, "%s: %llu records, max_recs is %llu", who, (unsigned long long)tot[0],
+                     (unsigned long long)max_recs);
+  if (gather && tot[2] > max_bytes)
+    return set_error(GPD_ERR_INVALID, "%s: %llu bytes, max_bytes is %llu", who, (unsigned long long)tot[2],
+                     (unsigned long long)max_bytes);
+  A.nrecs = (uint32_t)tot[0];
+  A.nbytes = tot[2];
+  hipLaunchKernelGGL(ta_place_kernel, dim3(wgrid), dim3(64 * kWalkWaves), 0, s, A);
+  if (gather && A.nrecs && A.nbytes) {
+    const uint32_t nwave = (A.nrecs + 63u) / 64u;
+    hipLaunchKernelGGL(ta_gather_kernel, dim3((nwave + kGatherWaves - 1u) / kGatherWaves), dim3(64 * kGatherWaves), 0,
+                       s, A);
+  }
+  TA_TRY(hipGetLastError());
+  TA_TRY(hipStreamSynchronize(s));
+  return GPD_OK;
+}
