@@ -7,8 +7,9 @@ reading (results.py), input formats (pcap.py, pcapng.py, afpacket.py, synth.py),
 pcapng writers and batch selection (pcapwrite.py), BPF filtering of a device batch (bpf.py), the flow
 table (flows.py), the IPv4 fragment hand-off to ip4defrag (defrag.py) and the TCP segment
 hand-off to tcpassembly (tcpassembly.py) and the stream assembly over it (tcpstream.py: the
-Reassembly lists per connection, built on the device).  (ip4defrag, the stateful consumer of the
-fragment hand-off, is restated only as a test checker, oracle/ip4defrag_ref.py; the stream
+Reassembly lists per connection, built on the device) and the IPv4 defragmentation over the
+fragment hand-off (ip4reasm.py: ip4defrag's datagrams rebuilt on the device; its checker is the
+restated defragmenter oracle/ip4defrag_ref.py driven by tests/ip4reasm_ref.py).  (The stream
 assembler's restatement tests/tcpassembly_ref.py is the oracle of tcpstream.py.)
 """
 from . import layers
@@ -20,14 +21,14 @@ from .results import (BatchResult, Endpoint, FastHashes, Flow, FlowFromEndpoints
 
 __all__ = ["layers", "PacketBatch", "BatchResult", "DecodeError", "UnsupportedLayerType",
            "Endpoint", "Flow", "NewEndpoint", "NewFlow", "FlowFromEndpoints", "FastHashes",
-           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream"]
+           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm"]
 
 
 def __getattr__(name):
     # the parser pulls in libgpd.so; import it lazily so that pure-host helpers
     # (pcap, synth, layers) work in environments that only build.
-    # (pcapng, pcapwrite, bpf, tcpassembly and tcpstream bind their entry points onto libgpd.so too)
-    if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream"):
+    # (pcapng, pcapwrite, bpf, tcpassembly, tcpstream and ip4reasm bind their entry points onto libgpd.so too)
+    if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("NgWriter", "NewNgWriter", "NewNgWriterInterface"):  # the pcapng writer (pcapwrite.py)
