@@ -9,7 +9,9 @@ table (flows.py), the IPv4 fragment hand-off to ip4defrag (defrag.py) and the TC
 hand-off to tcpassembly (tcpassembly.py) and the stream assembly over it (tcpstream.py: the
 Reassembly lists per connection, built on the device) and the IPv4 defragmentation over the
 fragment hand-off (ip4reasm.py: ip4defrag's datagrams rebuilt on the device; its checker is the
-restated defragmenter oracle/ip4defrag_ref.py driven by tests/ip4reasm_ref.py).  (The stream
+restated defragmenter oracle/ip4defrag_ref.py driven by tests/ip4reasm_ref.py) and the stateful
+TCP assembler (tcpasm.py: tcpassembly's Assembler + StreamPool as a device object that keeps
+out-of-order data across batches, with FlushOlderThan / FlushAll).  (The stream
 assembler's restatement tests/tcpassembly_ref.py is the oracle of tcpstream.py.)
 """
 from . import layers
@@ -21,14 +23,14 @@ from .results import (BatchResult, Endpoint, FastHashes, Flow, FlowFromEndpoints
 
 __all__ = ["layers", "PacketBatch", "BatchResult", "DecodeError", "UnsupportedLayerType",
            "Endpoint", "Flow", "NewEndpoint", "NewFlow", "FlowFromEndpoints", "FastHashes",
-           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm"]
+           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm", "tcpasm"]
 
 
 def __getattr__(name):
     # the parser pulls in libgpd.so; import it lazily so that pure-host helpers
     # (pcap, synth, layers) work in environments that only build.
-    # (pcapng, pcapwrite, bpf, tcpassembly, tcpstream and ip4reasm bind their entry points onto libgpd.so too)
-    if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm"):
+    # (pcapng, pcapwrite, bpf, tcpassembly, tcpstream, ip4reasm and tcpasm bind their entry points onto libgpd.so too)
+    if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm", "tcpasm"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("NgWriter", "NewNgWriter", "NewNgWriterInterface"):  # the pcapng writer (pcapwrite.py)

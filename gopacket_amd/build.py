@@ -37,7 +37,8 @@ SOURCES = [*KERNEL_SOURCES, os.path.join(CSRC, "gpd_runtime.cpp"),
            os.path.join(CSRC, "gpd_ngwalk.hip"), os.path.join(CSRC, "gpd_pcapwrite.hip"),
            os.path.join(CSRC, "gpd_bpf.hip"), os.path.join(CSRC, "gpd_bpf_host.cpp"),
            os.path.join(CSRC, "gpd_tcpseg.hip"), os.path.join(CSRC, "gpd_pcapngwrite.hip"),
-           os.path.join(CSRC, "gpd_tcpstream.hip"), os.path.join(CSRC, "gpd_ip4reasm.hip")]
+           os.path.join(CSRC, "gpd_tcpstream.hip"), os.path.join(CSRC, "gpd_ip4reasm.hip"),
+           os.path.join(CSRC, "gpd_tcpasm.hip")]
 HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h"),
            os.path.join(CSRC, "gpd_segwalk.h"), os.path.join(CSRC, "gpd_launch.h"),
            os.path.join(CSRC, "gpd_compact.h"),
@@ -53,7 +54,8 @@ HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h")
            os.path.join(ROOT, "include", "gpd_pcapngwrite.h"),
            os.path.join(ROOT, "include", "gpd_tcpstream.h"), os.path.join(CSRC, "gpd_tcpstream_walk.h"),
            os.path.join(CSRC, "gpd_stream_util.h"),
-           os.path.join(ROOT, "include", "gpd_ip4reasm.h"), os.path.join(CSRC, "gpd_ip4reasm_walk.h")]
+           os.path.join(ROOT, "include", "gpd_ip4reasm.h"), os.path.join(CSRC, "gpd_ip4reasm_walk.h"),
+           os.path.join(ROOT, "include", "gpd_tcpasm.h"), os.path.join(CSRC, "gpd_tcpasm_walk.h")]
 
 
 def _stale(target, deps):

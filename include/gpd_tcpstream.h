@@ -29,7 +29,9 @@
  * Options.  max_pages_per_connection is AssemblerOptions.MaxBufferedPagesPerConnection
  * (:720-726; 0: no limit).  MaxBufferedPagesTotal couples all connections through one page
  * counter (a.pc.used, :721), so connections would no longer be independent: it is not offered.
- * FlushOlderThan by time (:269-271) is not offered either: step 2 is the only flush.
+ * FlushOlderThan by time (:269-271) is not offered either: step 2 is the only flush.  The flush
+ * by time, and out-of-order data that waits across batches, are what the stateful assembler of
+ * gpd_tcpasm.h (gpd_tcp_assembler_run) offers; this entry point stays as it is.
  *
  * Reference interfaces the entry point replaces:
  *   gpd_tcp_assemble   Assembler.AssembleWithTimestamp (:533-607) over whole connections,
