@@ -15,16 +15,16 @@ PAYLOAD_LENS = (0, 1, 3, 10, 100, 1460, 1900, 1901, 4000)
 PAYLOAD_WEIGHTS = (0.05, 0.12, 0.12, 0.25, 0.25, 0.10, 0.04, 0.04, 0.03)
 
 
-def gen_group(rng, max_segments=200):
+def gen_group(rng, max_segments=200, weights=PAYLOAD_WEIGHTS):
     """One group of 1..max_segments segments as (seq, flags, payload_len): a start sequence from
-    START_SEQS, payload lengths from PAYLOAD_LENS (0 only with a flag); after each segment the
-    next seq is in order (80 %), a gap of 1, 7 or 3000 (10 %) or a step back of 1, 2, 5 or 2000
-    (10 %); 3 % FIN, 2 % RST, 2 % SYN mid-stream; then local swaps within 3 positions."""
+    START_SEQS, payload lengths from PAYLOAD_LENS with `weights` (0 only with a flag); after each
+    segment the next seq is in order (80 %), a gap of 1, 7 or 3000 (10 %) or a step back of 1, 2, 5
+    or 2000 (10 %); 3 % FIN, 2 % RST, 2 % SYN mid-stream; then local swaps within 3 positions."""
     n = int(rng.integers(1, max_segments + 1))
     seq = int(START_SEQS[rng.integers(len(START_SEQS))])
     segs = []
     for i in range(n):
-        plen = int(PAYLOAD_LENS[rng.choice(len(PAYLOAD_LENS), p=PAYLOAD_WEIGHTS)])
+        plen = int(PAYLOAD_LENS[rng.choice(len(PAYLOAD_LENS), p=weights)])
         flags = 0
         u = rng.random()
         if i == 0 and rng.random() < 0.6:
@@ -51,9 +51,9 @@ def gen_group(rng, max_segments=200):
     return segs
 
 
-def gen_groups(seed, ngroups, max_segments=200):
+def gen_groups(seed, ngroups, max_segments=200, weights=PAYLOAD_WEIGHTS):
     rng = np.random.default_rng(seed)
-    return [gen_group(rng, max_segments) for _ in range(ngroups)]
+    return [gen_group(rng, max_segments, weights) for _ in range(ngroups)]
 
 
 def crafted(groups, keys=None, interleave_seed=None, fill_seed=1):

@@ -34,12 +34,12 @@ def frames(n, seed, mixed=False):
     return [b.data[o:o + c].tobytes() for o, c in zip(b.offset.tolist(), b.caplen.tolist())]
 
 
-def decode(raw, dw, flags=(False, False, False), steps=None):
+def decode(raw, dw, flags=(False, False, False), steps=None, chunk=CHUNK):
     """(fields, n, stop, err, next position, walk counts) of DecodePcapNg over the capture; with
     `steps`, in bounded calls of those sizes (the last repeated) continued to the stop."""
     from gopacket_amd import pcapng
     cap = raw if isinstance(raw, np.ndarray) else capture_array(raw)
-    rd = pcapng.NgReader(cap, pcapng.NgReaderOptions(*flags, device_walk=dw, chunk_bytes=CHUNK))
+    rd = pcapng.NgReader(cap, pcapng.NgReaderOptions(*flags, device_walk=dw, chunk_bytes=chunk))
     p = _parser()
     if steps is None:
         res, n, stop, err = p.DecodePcapNg(rd, nthreads=8)
@@ -66,11 +66,11 @@ def same(a, b):
         assert np.array_equal(a[0][f], b[0][f]), f
 
 
-def both(raw, flags=(False, False, False)):
+def both(raw, flags=(False, False, False), chunk=CHUNK):
     """Device walk == host walk == DecodeBatchHost of the indexed batch; returns the device walk's."""
     from gopacket_amd import pcapng
     cap = raw if isinstance(raw, np.ndarray) else capture_array(raw)
-    dev, host = decode(cap, 1, flags), decode(cap, 0, flags)
+    dev, host = decode(cap, 1, flags, chunk=chunk), decode(cap, 0, flags, chunk=chunk)
     same(dev, host)
     assert host[5][0] == 0  # the host walk sends no chunk through the device walk
     idx = pcapng.NgReader(cap, pcapng.NgReaderOptions(*flags)).ReadAll()
@@ -96,6 +96,29 @@ def test_imix_jumbo_and_empty_packets_stay_on_the_device():
     got, n, stop, err, pos, c = both(raw)
     assert (n, stop, err, pos) == (4096, 1, None, len(raw))
     assert c[0] >= len(raw) // CHUNK and c[1] == 0 and c[2] == 0, c
+
+
+def test_stitch_lanes_own_several_segments():
+    """ng_stitch_kernel (gpd_segwalk.h seg_stitch_body): lane t of its one workgroup owns
+    ceil(nseg / 1024) consecutive 2,048-byte segments, one with the 64 KiB chunks of the other
+    tests.  Chunks of 4 MiB + 4 KiB have 2,050 segments: three a lane, the last owning lane one,
+    the lanes behind it none; the capture's last chunk is shorter (two a lane).  Jumbo blocks
+    make segments no header starts in, empty packets and a refuted speculation's re-walk
+    (payloads that look like block headers) move the counts the lanes add up."""
+    chunk = (1 << 22) + 4096
+    pk = frames(28000, 0x62)
+    rng = np.random.default_rng(0x62)
+    for i in rng.choice(len(pk), size=40, replace=False):
+        pk[i] = pk[i] + bytes(rng.integers(0, 256, size=9000 - len(pk[i]), dtype=np.uint8))
+    for i in rng.choice(len(pk), size=16, replace=False):
+        pk[i] = b""
+    for i in rng.choice(len(pk), size=16, replace=False):  # an enhanced packet block's first words, as payload
+        pk[i] = struct.pack("<IIIIIII", 6, 96, 0, 0, i, 64, 64) * 3
+    raw = head() + b"".join(S.epb(p, ts=i) for i, p in enumerate(pk))
+    assert 2 * chunk < len(raw) < 3 * chunk and (len(raw) - 2 * chunk) // 2048 > 1024
+    got, n, stop, err, pos, c = both(raw, chunk=chunk)
+    assert (n, stop, err, pos) == (len(pk), 1, None, len(raw))
+    assert c[0] == 3 and c[1] == 0 and c[2] == 0, c
 
 
 def test_block_header_at_every_position_around_a_chunk_edge():
