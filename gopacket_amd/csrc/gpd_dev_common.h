@@ -273,8 +273,13 @@ __device__ __forceinline__ uint32_t dot2(uint32_t x, uint32_t w, uint32_t acc) {
 // ~fold(S) (tcpip.go:66-69) from the little-endian-domain sum S' of the same 16-bit words:
 // the one's-complement sum of byte-swapped words is the byte-swapped sum (RFC 1071 §2(B)),
 // exactly — an all-zero input gives 0 in both domains, anything else a value in
-// [1, 0xFFFF] congruent mod 0xFFFF — as long as neither sum wraps 2^32 (true for the
-// <= 16 KiB a fast-path packet spans).  Two folds bring any u32 to <= 0xFFFF.
+// [1, 0xFFFF] congruent mod 0xFFFF — as long as neither sum wraps 2^32.  That holds for every
+// segment the fast decoders sum: its length comes from a 16-bit IP length (a jumbogram's
+// hop-by-hop header sends it to the generic decoder), so it has at most 65,535 bytes = 32,768
+// words of at most 0xFFFF each, 0x7FFF8000, and the pseudo-header adds at most 18 words
+// (32 address bytes, protocol, length): below 2^31 + 2^21 in either byte order — ro_kernel feeds
+// such 64-KiB segments, the windowed kernels at most a window.  Two folds bring any u32 to
+// <= 0xFFFF (tests/csum_cases.py folds(): the sums whose second fold carries in one domain only).
 __device__ __forceinline__ uint32_t fold_le_not(uint32_t s) {
   s = (s >> 16) + (s & 0xFFFFu);
   s = (s >> 16) + (s & 0xFFFFu);

@@ -18,33 +18,37 @@ def eth(ethertype: int, payload: bytes) -> bytes:
 
 
 def ip4(payload: bytes, proto: int = 6, ihl: int = 5, length=None, opts: bytes = b"",
-        flags_frag: int = 0) -> bytes:
+        flags_frag: int = 0, tos: int = 0, ident: int = 0x1234, ttl: int = 64, csum: int = 0,
+        src: bytes = bytes([10, 0, 0, 1]), dst: bytes = bytes([10, 0, 0, 2])) -> bytes:
     hdr = bytearray(20) + bytearray(opts)
     hdr[0] = 0x40 | ihl
+    hdr[1] = tos
     total = len(hdr) + len(payload) if length is None else length
-    struct.pack_into(">HHHBB", hdr, 2, total, 0x1234, flags_frag, 64, proto)
-    hdr[12:16] = bytes([10, 0, 0, 1])
-    hdr[16:20] = bytes([10, 0, 0, 2])
+    struct.pack_into(">HHHBBH", hdr, 2, total, ident, flags_frag, ttl, proto, csum)
+    hdr[12:16] = src
+    hdr[16:20] = dst
     return bytes(hdr) + payload
 
 
-def ip6(payload: bytes, nh: int = 6, length=None) -> bytes:
+def ip6(payload: bytes, nh: int = 6, length=None, tc_flow: int = 0, hlim: int = 64,
+        src: bytes = bytes(range(16)), dst: bytes = bytes(range(16, 32))) -> bytes:
     hdr = bytearray(40)
-    hdr[0] = 0x60
-    struct.pack_into(">HBB", hdr, 4, len(payload) if length is None else length, nh, 64)
-    hdr[8:24] = bytes(range(16))
-    hdr[24:40] = bytes(range(16, 32))
+    struct.pack_into(">I", hdr, 0, 0x60000000 | (tc_flow & 0x0FFFFFFF))
+    struct.pack_into(">HBB", hdr, 4, len(payload) if length is None else length, nh, hlim)
+    hdr[8:24] = src
+    hdr[24:40] = dst
     return bytes(hdr) + payload
 
 
-def tcp(payload: bytes = b"", doff: int = 5, opts: bytes = b"", sport=40000, dport=8080) -> bytes:
+def tcp(payload: bytes = b"", doff: int = 5, opts: bytes = b"", sport=40000, dport=8080, seq: int = 1,
+        ack: int = 2, window: int = 0, csum: int = 0) -> bytes:
     hdr = bytearray(20) + bytearray(opts)
-    struct.pack_into(">HHIIBB", hdr, 0, sport, dport, 1, 2, doff << 4, 0x18)
+    struct.pack_into(">HHIIBBHH", hdr, 0, sport, dport, seq, ack, doff << 4, 0x18, window, csum)
     return bytes(hdr) + payload
 
 
-def udp(payload: bytes = b"", length=None, sport=40000, dport=8080) -> bytes:
-    return struct.pack(">HHHH", sport, dport, 8 + len(payload) if length is None else length, 0) + payload
+def udp(payload: bytes = b"", length=None, sport=40000, dport=8080, csum: int = 0) -> bytes:
+    return struct.pack(">HHHH", sport, dport, 8 + len(payload) if length is None else length, csum) + payload
 
 
 # (name, packet, code, arg0, arg1): the reference site each case reaches (paths relative to

@@ -10,6 +10,8 @@ from __future__ import annotations
 import json
 import os
 
+import numpy as np
+
 import golden_cases as G
 from gopacket_amd import layers as L
 from gopacket_amd.batch import PacketBatch
@@ -55,10 +57,10 @@ def _fold_not(s: int) -> int:
 
 
 def _words(b: bytes) -> int:
-    s = sum((b[i] << 8) | b[i + 1] for i in range(0, len(b) - 1, 2))
-    if len(b) % 2:
-        s += b[-1] << 8
-    return s
+    """The unreduced sum of the big-endian 16-bit words of b, an odd last byte counted << 8
+    (tcpip.go:57-65), as a Python integer: the bytes at even positions weigh 256."""
+    a = np.frombuffer(bytes(b), np.uint8)
+    return (int(a[0::2].sum(dtype=np.uint64)) << 8) + int(a[1::2].sum(dtype=np.uint64))
 
 
 def ip4_checksum(h: bytes) -> int:
@@ -67,13 +69,20 @@ def ip4_checksum(h: bytes) -> int:
     return _fold_not(_words(bytes(h)))
 
 
-def l4_checksum(pkt: bytes, a: int, b: int, net_kind: str, net_off: int, proto: int) -> int:
+def l4_sum(pkt: bytes, a: int, b: int, net_kind: str, net_off: int, proto: int) -> int:
+    """computeChecksum's sum before Go's uint32 drops anything (tcpip.go:26-48,75-88): the
+    pseudo-header addresses, the protocol, length & 0xffff and length >> 16, then the segment's
+    words.  _fold_not makes the wrap explicit."""
     if net_kind == "IPv4":
         ps = _words(pkt[net_off + 12:net_off + 20])
     else:
         ps = _words(pkt[net_off + 8:net_off + 40])
     n = b - a
-    return _fold_not(ps + proto + (n & 0xFFFF) + (n >> 16) + _words(pkt[a:b]))
+    return ps + proto + (n & 0xFFFF) + (n >> 16) + _words(pkt[a:b])
+
+
+def l4_checksum(pkt: bytes, a: int, b: int, net_kind: str, net_off: int, proto: int) -> int:
+    return _fold_not(l4_sum(pkt, a, b, net_kind, net_off, proto))
 
 
 def expected(c):

@@ -399,9 +399,10 @@ def _ip4_option_frames(n, seed):
 
 @pytest.mark.parametrize("ho", [0, 1, 2])
 def test_ip4_options_both_ways(ho):
-    """IPv4 options on long frames: the header-once kernel walks them in seg_pass (ip4_options)
-    and decodes the packets in its straight-line pass; the per-window kernel leaves them to the
-    generic decoder.  Both against the oracle, valid and erroneous options alike."""
+    """IPv4 options on long frames: hdr_parse and fast_decode take IHL 5 only, so every kernel —
+    per window, header-once per window and per round — leaves these packets to the generic
+    decoder (DESIGN.md §5 "Fallback"; tests/test_csum_extremes_gpu.py asserts the count).  Each
+    against the oracle, valid and erroneous options alike."""
     t = dict(window_bytes=8192, header_once=ho)
     run_both(PacketBatch.from_packets(_ip4_option_frames(1 << 12, 0x5EED0501)), ext=False, tuning=t)
     pk = _ip4_option_frames(1 << 11, 0x5EED0502)
