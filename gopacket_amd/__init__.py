@@ -11,7 +11,9 @@ Reassembly lists per connection, built on the device) and the IPv4 defragmentati
 fragment hand-off (ip4reasm.py: ip4defrag's datagrams rebuilt on the device; its checker is the
 restated defragmenter oracle/ip4defrag_ref.py driven by tests/ip4reasm_ref.py) and the stateful
 TCP assembler (tcpasm.py: tcpassembly's Assembler + StreamPool as a device object that keeps
-out-of-order data across batches, with FlushOlderThan / FlushAll).  (The stream
+out-of-order data across batches, with FlushOlderThan / FlushAll) and TCP connection tracking
+(tcptrack.py: reassembly's bidirectional connection, packet direction and TCPSimpleFSM verdicts,
+one state machine per connection kept on the device; its model is tests/tcptrack_ref.py).  (The stream
 assembler's restatement tests/tcpassembly_ref.py is the oracle of tcpstream.py.)
 """
 from . import layers
@@ -23,14 +25,16 @@ from .results import (BatchResult, Endpoint, FastHashes, Flow, FlowFromEndpoints
 
 __all__ = ["layers", "PacketBatch", "BatchResult", "DecodeError", "UnsupportedLayerType",
            "Endpoint", "Flow", "NewEndpoint", "NewFlow", "FlowFromEndpoints", "FastHashes",
-           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm", "tcpasm"]
+           "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm", "tcpasm",
+           "tcptrack"]
 
 
 def __getattr__(name):
     # the parser pulls in libgpd.so; import it lazily so that pure-host helpers
     # (pcap, synth, layers) work in environments that only build.
-    # (pcapng, pcapwrite, bpf, tcpassembly, tcpstream, ip4reasm and tcpasm bind their entry points onto libgpd.so too)
-    if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm", "tcpasm"):
+    # (pcapng, pcapwrite, bpf, tcpassembly, tcpstream, ip4reasm, tcpasm and tcptrack bind their entry points onto libgpd.so too)
+    if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm", "tcpasm",
+                "tcptrack"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("NgWriter", "NewNgWriter", "NewNgWriterInterface"):  # the pcapng writer (pcapwrite.py)

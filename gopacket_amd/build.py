@@ -38,7 +38,7 @@ SOURCES = [*KERNEL_SOURCES, os.path.join(CSRC, "gpd_runtime.cpp"),
            os.path.join(CSRC, "gpd_bpf.hip"), os.path.join(CSRC, "gpd_bpf_host.cpp"),
            os.path.join(CSRC, "gpd_tcpseg.hip"), os.path.join(CSRC, "gpd_pcapngwrite.hip"),
            os.path.join(CSRC, "gpd_tcpstream.hip"), os.path.join(CSRC, "gpd_ip4reasm.hip"),
-           os.path.join(CSRC, "gpd_tcpasm.hip")]
+           os.path.join(CSRC, "gpd_tcpasm.hip"), os.path.join(CSRC, "gpd_tcptrack.hip")]
 HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h"),
            os.path.join(CSRC, "gpd_segwalk.h"), os.path.join(CSRC, "gpd_launch.h"),
            os.path.join(CSRC, "gpd_compact.h"),
@@ -55,7 +55,9 @@ HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h")
            os.path.join(ROOT, "include", "gpd_tcpstream.h"), os.path.join(CSRC, "gpd_tcpstream_walk.h"),
            os.path.join(CSRC, "gpd_stream_util.h"),
            os.path.join(ROOT, "include", "gpd_ip4reasm.h"), os.path.join(CSRC, "gpd_ip4reasm_walk.h"),
-           os.path.join(ROOT, "include", "gpd_tcpasm.h"), os.path.join(CSRC, "gpd_tcpasm_walk.h")]
+           os.path.join(ROOT, "include", "gpd_tcpasm.h"), os.path.join(CSRC, "gpd_tcpasm_walk.h"),
+           os.path.join(ROOT, "include", "gpd_tcptrack.h"), os.path.join(CSRC, "gpd_tcptrack_fsm.h"),
+           os.path.join(CSRC, "gpd_radix_sort.h")]
 
 
 def _stale(target, deps):

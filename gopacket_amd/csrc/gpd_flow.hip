@@ -550,6 +550,51 @@ __global__ __launch_bounds__(kFlowThreads) void flow_ids_scatter_kernel(const gp
   }
 }
 
+// The connection tracker's peer lookup (gpd_internal.h PeerArgs): one lane per tracked packet.
+// The probe is read-only and follows the insert's sequence for the reversed key's fingerprint: an
+// empty slot ends it (no record), the first slot with the fingerprint ends it (the insert
+// stops there too: a different key under that fingerprint is a collision, and its packets got no
+// record).  The loads that do not depend on the probe — the packet's flag byte, its own
+// record's `first` and carried byte — are issued before it, and the peer's `first` and carried
+// byte together after it, ahead of the compare that picks the connection.
+__global__ __launch_bounds__(kFlowThreads) void flow_peer_kernel(FlowParams P, PeerArgs A) {
+  for (uint32_t j = blockIdx.x * (uint32_t)kFlowThreads + threadIdx.x; j < A.cnt;
+       j += gridDim.x * (uint32_t)kFlowThreads) {
+    const uint32_t i = A.idx[j];
+    const uint32_t f = A.flow_id[i];  // below the capacity: the tracker's count kept the packet
+    uint32_t k[10];
+    (void)flow_key(P, i, k);  // (true, for the same reason)
+    const uint64_t first_f = P.cold[f].first;
+    const uint32_t carried_f = A.carried[f];
+    const uint64_t off = min((uint64_t)P.offset[i], P.data_len);
+    const uint64_t fb = off + (P.hdr_off[i] >> 16) + 13u;  // tcp.go:241-249: header byte 13
+    const uint32_t tf = fb < P.data_len ? P.data[fb] : 0u;
+    const uint32_t rk[10] = {k[4], k[5], k[6], k[7], k[0], k[1], k[2], k[3], (k[8] >> 16) | (k[8] << 16), k[9]};
+    const uint64_t fp = fingerprint(rk, P.fp_mask);
+    uint64_t s = fp & P.mask;
+    uint32_t r = GPD_FLOW_NONE;
+    for (uint64_t probe = 0; probe <= P.mask; probe++) {
+      const uint64_t old = P.tab[s].fp;
+      if (old == 0ull) break;
+      if ((old & kFpBits) == fp) {
+        if (same_key(P.tab[s], rk)) r = (uint32_t)s;
+        break;
+      }
+      s = (s + 1) & P.mask;
+    }
+    const uint32_t rr = r == GPD_FLOW_NONE ? f : r;
+    const uint64_t first_r = P.cold[rr].first;
+    const uint32_t carried_r = A.carried[rr];
+    const bool rev = first_r < first_f;  // (never with rr == f)
+    const uint32_t c = rev ? rr : f;
+    const uint32_t code = ((tf >> 1) & 1u) | (((tf >> 4) & 1u) << 1) | ((tf & 1u) << 2) | (((tf >> 2) & 1u) << 3) |
+                          ((uint32_t)rev << 4);
+    A.pairs[j] = make_uint2(c, j);
+    A.info[j] = code | ((rev ? carried_r : carried_f) << 8);
+    if (A.conn_id) A.conn_id[i] = c;
+  }
+}
+
 __global__ __launch_bounds__(kFlowThreads) void flow_reset_kernel(FlowHot *tab, FlowCold *cold, uint64_t cap) {
   for (uint64_t s = blockIdx.x * (uint64_t)kFlowThreads + threadIdx.x; s < cap;
        s += (uint64_t)gridDim.x * kFlowThreads) {
@@ -627,6 +672,21 @@ static unsigned grid_for(uint64_t work, int num_cus) {
   const uint64_t blocks = (work + gpd::kFlowThreads - 1) / gpd::kFlowThreads;
   return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)num_cus * 8));
 }
+
+namespace gpd {
+uint64_t flow_capacity(const gpd_flowtable *ft) { return ft->cap; }
+int flow_device(const gpd_flowtable *ft) { return ft->device; }
+hipError_t launch_flow_peers(const gpd_flowtable *ft, const PeerArgs &A, hipStream_t stream) {
+  if (A.cnt == 0) return hipSuccess;
+  FlowParams P{A.data, A.data_len, A.offset, nullptr, A.status, A.hdr_off, nullptr, 0, 0, ft->tab,
+               ft->cap - 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  P.fp_mask = ft->fp_mask;
+  P.rec = A.rec;
+  P.cold = ft->cold;
+  hipLaunchKernelGGL(flow_peer_kernel, dim3(grid_for(A.cnt, ft->num_cus)), dim3(kFlowThreads), 0, stream, P, A);
+  return hipGetLastError();
+}
+}  // namespace gpd
 
 static hipError_t grow_made(gpd_flowtable *ft, uint64_t n) {
   const uint64_t words = (n + 63) / 64;

@@ -211,6 +211,33 @@ struct FragArgs {
 };
 hipError_t launch_ip4_frag(const FragArgs &A, hipStream_t stream, int num_cus);
 
+// The connection tracker's peer lookup (include/gpd_tcptrack.h; the kernel is in gpd_flow.hip,
+// which owns the slot layout).  For tracked packet j = idx[j] of the batch, with flow id f: the
+// record r of the reversed key by a read-only probe, both records' `first`, and
+//   pairs[j] = (c, j)        c = whichever of f and r has the smaller `first` (f without r)
+//   info[j]  = code | carried[c] << 8     code: SYN 1, ACK 2, FIN 4, RST 8, c != f 16
+//   conn_id[idx[j]] = c      (when conn_id is not NULL)
+// Run it after the batch's gpd_flow_insert, on the same stream.
+}  // namespace gpd
+struct gpd_flowtable;
+namespace gpd {
+struct PeerArgs {
+  const uint8_t *data;
+  uint64_t data_len;
+  const uint32_t *offset, *status, *hdr_off;
+  const gpd_record *rec;    // results in the gpd_record form (status there)
+  const uint32_t *flow_id;  // the batch's flow ids
+  const uint32_t *idx;      // the tracked packets, in order
+  uint32_t cnt;
+  const uint8_t *carried;   // one byte per flow record
+  uint2 *pairs;
+  uint32_t *info;
+  uint32_t *conn_id;
+};
+hipError_t launch_flow_peers(const gpd_flowtable *ft, const PeerArgs &A, hipStream_t stream);
+uint64_t flow_capacity(const gpd_flowtable *ft);
+int flow_device(const gpd_flowtable *ft);
+
 // One launch covers at most this many packets, so packet and tile indices are 32-bit.
 constexpr uint64_t kMaxLaunchPackets = 1ull << 30;
 

@@ -15,6 +15,7 @@
 //   ts_index_kernel     the kept packets' indices in order, from the mask words
 //   ts_record_kernel    one lane per segment: the 32-byte record (in packet order), and with
 //                       grouping its (key, index) pair
+//   (the three sort kernels live in gpd_radix_sort.h, shared with gpd_tcptrack.hip)
 //   sort_hist_kernel    per workgroup tile of kSortTile pairs: counts per digit, [digit][tile]
 //   sort_scan_kernel    one workgroup: exclusive scan of the [digit][tile] counts in place
 //   sort_scatter_kernel stable ranks inside the tile: per wave eight ballots give the lanes
@@ -32,10 +33,9 @@
 // TCP object's exact BaseLayer, as the fragment hand-off does for the IPv4 object.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "gpd_compact.h"
 #include "gpd_dev_generic.h"
+#include "gpd_radix_sort.h"
 #include "../../include/gpd_flow.h"
 #include "../../include/gpd_tcpassembly.h"
 
@@ -45,11 +45,6 @@ namespace {
 static_assert(sizeof(gpd_tcp_seg) == 32 && sizeof(gpd_tcp_group) == 16, "include/gpd_tcpassembly.h layouts");
 
 constexpr uint32_t kCountBlock = kCompactBlock;  // items per counting workgroup
-constexpr uint32_t kSortThreads = 1024;
-constexpr uint32_t kSortWaves = kSortThreads / 64u;
-constexpr uint32_t kSortRounds = 8;     // pairs per lane
-constexpr uint32_t kSortTile = kSortThreads * kSortRounds;  // pairs per workgroup (tcpassembly.SORT_TILE)
-constexpr uint32_t kWaveSpan = 64u * kSortRounds;           // consecutive pairs of one wave
 
 struct TsArgs {
   KParams P;
@@ -210,139 +205,22 @@ __global__ __launch_bounds__(256) void ts_record_kernel(TsArgs A) {
   }
 }
 
-// ---- the radix sort ----------------------------------------------------------------------------
-// The lanes of the wave whose digit equals this lane's (invalid lanes match nobody): eight
-// ballots, one per bit.  Called by all 64 lanes.
-__device__ __forceinline__ uint64_t match_digit(bool valid, uint32_t d) {
-  uint64_t m = __ballot(valid);
-#pragma unroll
-  for (uint32_t b = 0; b < 8u; ++b) {
-    const bool bit = (d >> b) & 1u;
-    const uint64_t bal = __ballot(valid && bit);
-    m &= bit ? bal : ~bal;
+// ---- the radix sort (gpd_radix_sort.h) -----------------------------------------------------------
+// The last pass's sink: the record of the pair's segment goes to its final place, with the key
+// beside it for the groups.
+struct SegSink {
+  const gpd_tcp_seg *tmp;
+  gpd_tcp_seg *segs;
+  uint32_t *skey;
+  __device__ __forceinline__ void operator()(uint32_t pos, uint2 p) const {
+    const uint4 *s = reinterpret_cast<const uint4 *>(tmp + p.y);
+    const uint4 s0 = s[0], s1 = s[1];
+    uint4 *q = reinterpret_cast<uint4 *>(segs + pos);
+    q[0] = s0;
+    q[1] = s1;
+    skey[pos] = p.x;
   }
-  return m;
-}
-
-// A wave owns kWaveSpan consecutive pairs of its workgroup's tile, lane l those at l, l + 64, ...
-__device__ __forceinline__ uint32_t tile_item(uint32_t w, uint32_t lane, uint32_t r) {
-  return blockIdx.x * kSortTile + w * kWaveSpan + r * 64u + lane;
-}
-
-__global__ __launch_bounds__(kSortThreads) void sort_hist_kernel(TsArgs A, const uint2 *in, uint32_t shift) {
-  __shared__ uint32_t h[256];
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  if (t < 256u) h[t] = 0;
-  __syncthreads();
-#pragma unroll
-  for (uint32_t r = 0; r < kSortRounds; ++r) {
-    const uint32_t j = tile_item(w, lane, r);
-    const bool valid = j < A.cnt;
-    const uint32_t d = valid ? (in[j].x >> shift) & 255u : 0u;
-    const uint64_t m = match_digit(valid, d);
-    if (valid && (m & ((1ull << lane) - 1ull)) == 0ull) atomicAdd(&h[d], (uint32_t)__popcll(m));
-  }
-  __syncthreads();
-  if (t < 256u) A.hist[t * A.ntile + blockIdx.x] = h[t];
-}
-
-// One workgroup: exclusive scan of hist[256 * ntile] in place, sixteen consecutive entries a lane
-// a round (16,384 entries between barriers: 2^24 pairs make 2^19 entries, 32 rounds).
-__global__ __launch_bounds__(1024) void sort_scan_kernel(TsArgs A) {
-  __shared__ uint32_t wtot[16];
-  __shared__ uint32_t carry;
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  const uint32_t nent = 256u * A.ntile;  // a multiple of 16
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (uint32_t c0 = 0; c0 < nent; c0 += 16384u) {
-    const uint32_t k = c0 + 16u * t;
-    uint4 v[4];
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < 4u; ++q) {
-      v[q] = k < nent ? *reinterpret_cast<const uint4 *>(A.hist + k + 4u * q) : make_uint4(0u, 0u, 0u, 0u);
-      s += v[q].x + v[q].y + v[q].z + v[q].w;
-    }
-    const uint32_t x = wave_scan32(s, lane);
-    if (lane == 63u) wtot[w] = x;
-    __syncthreads();
-    uint32_t before = carry;
-    for (uint32_t j = 0; j < w; ++j) before += wtot[j];
-    uint32_t e = before + x - s;
-    if (k < nent) {
-#pragma unroll
-      for (uint32_t q = 0; q < 4u; ++q) {
-        *reinterpret_cast<uint4 *>(A.hist + k + 4u * q) = make_uint4(e, e + v[q].x, e + v[q].x + v[q].y,
-                                                                     e + v[q].x + v[q].y + v[q].z);
-        e += v[q].x + v[q].y + v[q].z + v[q].w;
-      }
-    }
-    __syncthreads();
-    if (t == 1023u) carry = before + x;
-    __syncthreads();
-  }
-}
-
-// Stable scatter of one tile.  base[w][d] ends up as the place of wave w's first pair with digit
-// d: the tile's scanned [d][tile] word plus the counts of the waves before it; inside the wave a
-// pair's rank is the pairs of its digit in earlier rounds (the leader lane moves the base on)
-// plus the matching lanes below it.  LAST: the record of the pair's segment goes to its final
-// place, with the key beside it for the groups.
-template <bool LAST>
-__global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(TsArgs A, const uint2 *in, uint2 *out,
-                                                                      uint32_t shift) {
-  __shared__ uint32_t base[kSortWaves][256];
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  for (uint32_t k = t; k < kSortWaves * 256u; k += kSortThreads) (&base[0][0])[k] = 0;
-  __syncthreads();
-  uint2 p[kSortRounds];
-  uint32_t below[kSortRounds], tot[kSortRounds];
-#pragma unroll
-  for (uint32_t r = 0; r < kSortRounds; ++r) {
-    const uint32_t j = tile_item(w, lane, r);
-    const bool valid = j < A.cnt;
-    p[r] = valid ? in[j] : make_uint2(0u, 0u);
-    const uint32_t d = (p[r].x >> shift) & 255u;
-    const uint64_t m = match_digit(valid, d);
-    below[r] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    tot[r] = (valid && below[r] == 0u) ? (uint32_t)__popcll(m) : 0u;  // the digit's leader lane
-    if (tot[r]) base[w][d] += tot[r];  // (one leader per digit: no two lanes on one word)
-    __builtin_amdgcn_wave_barrier();   // rounds stay in order across the wave's lanes
-  }
-  __syncthreads();
-  if (t < 256u) {
-    uint32_t b = A.hist[t * A.ntile + blockIdx.x];
-    for (uint32_t k = 0; k < kSortWaves; ++k) {
-      const uint32_t c = base[k][t];
-      base[k][t] = b;
-      b += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (uint32_t r = 0; r < kSortRounds; ++r) {
-    const bool valid = tile_item(w, lane, r) < A.cnt;
-    const uint32_t d = (p[r].x >> shift) & 255u;
-    const uint32_t b = base[w][d];  // every lane reads before the leader moves it on
-    __builtin_amdgcn_wave_barrier();
-    if (tot[r]) base[w][d] = b + tot[r];
-    __builtin_amdgcn_wave_barrier();
-    if (valid) {
-      const uint32_t pos = b + below[r];
-      if (LAST) {
-        const uint4 *s = reinterpret_cast<const uint4 *>(A.tmp + p[r].y);
-        const uint4 s0 = s[0], s1 = s[1];
-        uint4 *q = reinterpret_cast<uint4 *>(A.segs + pos);
-        q[0] = s0;
-        q[1] = s1;
-        A.skey[pos] = p[r].x;
-      } else {
-        out[pos] = p[r];
-      }
-    }
-  }
-}
+};
 
 // One lane per group: heads[g] (idx) is where it starts.  The last lane leaves the counts.
 __global__ __launch_bounds__(256) void ts_group_kernel(TsArgs A) {
@@ -367,13 +245,6 @@ __global__ __launch_bounds__(256) void ts_group_kernel(TsArgs A) {
   } while (0)
 
 inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-
-// Passes of the sort: ceil(bitlen(id_bound) / 8), at least one (keys lie in [0, id_bound]).
-inline uint32_t sort_passes(uint32_t id_bound) {
-  uint32_t bits = 0;
-  for (uint32_t v = id_bound; v; v >>= 1) ++bits;
-  return std::max(1u, (bits + 7u) / 8u);
-}
 
 }  // namespace
 }  // namespace gpd
@@ -465,17 +336,10 @@ extern "C" int gpd_tcp_segments(gpd_ctx *ctx, const gpd_batch *in, const gpd_res
     TS_TRY(hipStreamSynchronize(s));
     return GPD_OK;
   }
-  const uint32_t passes = sort_passes(id_bound);
-  uint2 *src = A.pa, *dst = A.pb;
-  for (uint32_t p = 0; p < passes; ++p) {
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(A.ntile), dim3(kSortThreads), 0, s, A, src, 8u * p);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(1024), 0, s, A);
-    if (p + 1 == passes)
-      hipLaunchKernelGGL(sort_scatter_kernel<true>, dim3(A.ntile), dim3(kSortThreads), 0, s, A, src, dst, 8u * p);
-    else
-      hipLaunchKernelGGL(sort_scatter_kernel<false>, dim3(A.ntile), dim3(kSortThreads), 0, s, A, src, dst, 8u * p);
-    std::swap(src, dst);
-  }
+  const SortArgs S{total, A.ntile, A.hist};
+  const uint32_t passes = sort_passes(id_bound);  // keys lie in [0, id_bound]
+  const uint2 *src = sort_leading_passes(S, A.pa, A.pb, passes, s);
+  sort_last_pass(S, src, passes, SegSink{A.tmp, A.segs, A.skey}, s);
   // the groups: the compaction again, over the sorted keys' head flags
   A.nblk = (total + kCountBlock - 1u) / kCountBlock;
   TS_TRY(hipMemsetAsync(A.res, 0, 16, s));
