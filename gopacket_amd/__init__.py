@@ -13,7 +13,9 @@ restated defragmenter oracle/ip4defrag_ref.py driven by tests/ip4reasm_ref.py) a
 TCP assembler (tcpasm.py: tcpassembly's Assembler + StreamPool as a device object that keeps
 out-of-order data across batches, with FlushOlderThan / FlushAll) and TCP connection tracking
 (tcptrack.py: reassembly's bidirectional connection, packet direction and TCPSimpleFSM verdicts,
-one state machine per connection kept on the device; its model is tests/tcptrack_ref.py).  (The stream
+one state machine per connection kept on the device; its model is tests/tcptrack_ref.py) and flow expiry
+(flowexpire.py: idle flow records removed and their slots reused, so that all of these can run
+without a table reset; its model is tests/flow_expire_ref.py).  (The stream
 assembler's restatement tests/tcpassembly_ref.py is the oracle of tcpstream.py.)
 """
 from . import layers
@@ -26,15 +28,15 @@ from .results import (BatchResult, Endpoint, FastHashes, Flow, FlowFromEndpoints
 __all__ = ["layers", "PacketBatch", "BatchResult", "DecodeError", "UnsupportedLayerType",
            "Endpoint", "Flow", "NewEndpoint", "NewFlow", "FlowFromEndpoints", "FastHashes",
            "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm", "tcpasm",
-           "tcptrack"]
+           "tcptrack", "flowexpire"]
 
 
 def __getattr__(name):
     # the parser pulls in libgpd.so; import it lazily so that pure-host helpers
     # (pcap, synth, layers) work in environments that only build.
-    # (pcapng, pcapwrite, bpf, tcpassembly, tcpstream, ip4reasm, tcpasm and tcptrack bind their entry points onto libgpd.so too)
+    # (pcapng, pcapwrite, bpf, tcpassembly, tcpstream, ip4reasm, tcpasm, tcptrack and flowexpire bind their entry points onto libgpd.so too)
     if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm", "tcpasm",
-                "tcptrack"):
+                "tcptrack", "flowexpire"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("NgWriter", "NewNgWriter", "NewNgWriterInterface"):  # the pcapng writer (pcapwrite.py)

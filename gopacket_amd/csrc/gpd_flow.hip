@@ -26,6 +26,10 @@
 // travels as a 64-byte record to the rank its FastHash pair names; two passes (count per
 // owner, then scatter with wave-aggregated cursors) group the records by owner without a
 // sort, and the owner inserts records exactly as packets.
+// Records leave, too (include/gpd_flow_expire.h; slot rules in gpd_flow_slots.h): a removed
+// record's fingerprint word becomes a tombstone that probes walk past, inserts into a table that
+// may hold tombstones run an instantiation that claims them before empty slots, and a sweep
+// turns every run of tombstones that ends at an empty slot back into empty slots.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -33,14 +37,17 @@
 #include <vector>
 
 #include "gpd_internal.h"
+#include "gpd_compact.h"
+#include "gpd_flow_slots.h"
 #include "../../include/gpd_flow.h"
+#include "../../include/gpd_flow_expire.h"
 
 namespace gpd {
 
 constexpr int kFlowThreads = 256;
 static_assert(sizeof(gpd_flow_rec) == 80, "gpd_flow_rec layout (include/gpd_flow.h)");
 
-enum : uint32_t { FS_FLOWS = 0, FS_PACKETS, FS_NOKEY, FS_FULL, FS_COLL, FS_EXPORT, FS_WORDS = 8 };
+enum : uint32_t { FS_FLOWS = 0, FS_PACKETS, FS_NOKEY, FS_FULL, FS_COLL, FS_EXPORT, FS_LOAD_USED, FS_LOAD_TOMB, FS_WORDS = 8 };
 // The stats words lie 128 B apart: every wave adds its tallies when it ends, and device-scope
 // atomics on one line serialise at the memory side (~12 ns each), the words of a line together.
 constexpr uint32_t kStatStride = 16;
@@ -77,6 +84,7 @@ constexpr uint32_t kCountBits = 40;
 // boundary), and the insert updates and checks it at once; one claimed in this launch (or
 // 255 launches ago: deferring is always correct) is left to the verify launch.
 constexpr uint64_t kFpBits = (1ull << 56) - 1ull;
+static_assert(kFpBits == kSlotFpBits, "gpd_flow_slots.h reads the same fingerprint bits");
 
 struct FlowParams {
   const uint8_t *data;
@@ -293,7 +301,25 @@ __device__ __forceinline__ bool item_key(const FlowParams &P, uint64_t i, uint32
   }
 }
 
-template <bool KEYS>
+//
+// TOMBS: the table may hold tombstones (records removed since the last reset,
+// include/gpd_flow_expire.h); the host launches this instantiation only then, and TOMBS = false
+// is the code of a table that never had a removal.  The probe is gpd_flow_slots.h's step
+// function: a prober remembers the first tombstone on its chain, and where the chain ends without
+// its fingerprint (an empty slot, or the whole circle) it claims that tombstone with a
+// compare-and-swap tombstone -> fingerprint | tag, or without one the empty slot as before.
+// Within a launch a slot only ever goes (empty or tombstone) -> fingerprint, so what a prober
+// saw as a fingerprint is final, and a lost compare-and-swap means the slot holds a fingerprint
+// now: the lane resumes its probe at that slot (it may be its own key's) with nothing
+// remembered.  Every loss follows a slot turning into a fingerprint for good, so this converges.
+// No key is stored twice: take two lanes A and B with the same new key, and let B claim slot Y
+// first.  If A looks at Y after that, it finds its fingerprint there.  Otherwise A passed Y while
+// Y was a tombstone (an empty Y would have ended A's chain in a compare-and-swap on Y itself,
+// which B won), so A remembers a tombstone X at or before Y.  B claimed Y and not X, so when B
+// passed X it was no tombstone any more: another key had claimed it.  A's compare-and-swap on X
+// therefore fails, A rescans from X and reaches Y, which holds its fingerprint.  The same holds
+// when B claimed an empty slot: every tombstone before it was claimed before B passed it.
+template <bool KEYS, bool TOMBS>
 __global__ __launch_bounds__(kFlowThreads) void flow_insert_kernel(FlowParams P) {
   unsigned long long t_flows = 0, t_packets = 0, t_nokey = 0, t_full = 0, t_coll = 0;
   for (uint64_t i = blockIdx.x * (uint64_t)kFlowThreads + threadIdx.x; i - threadIdx.x < P.n;
@@ -313,7 +339,46 @@ __global__ __launch_bounds__(kFlowThreads) void flow_insert_kernel(FlowParams P)
     const uint64_t fp_prev = __shfl_up(fp, 1u, 64);
     const uint64_t lead = __ballot(!keyed || lane == 0u || fp_prev != fp);
     const bool probes = keyed && ((lead >> lane) & 1ull);
-    if (probes) {
+    if constexpr (TOMBS) {
+      if (probes) {
+        SlotProbe sp = slot_probe_begin(fp, P.mask);
+        const unsigned long long mine = (unsigned long long)(fp | P.tag);
+        unsigned long long word = *reinterpret_cast<volatile unsigned long long *>(&P.tab[sp.s].fp);
+        for (;;) {
+          const SlotStep st = slot_probe_step(sp, word, fp, P.mask);
+          if (st == STEP_NEXT) {
+            word = *reinterpret_cast<volatile unsigned long long *>(&P.tab[sp.s].fp);
+            continue;
+          }
+          if (st == STEP_MATCH) {
+            pre = (word & ~kFpBits) != P.tag;  // claimed by an earlier launch
+            break;
+          }
+          if (st == STEP_FULL) {
+            full = true;
+            break;
+          }
+          if (st == STEP_CLAIM_EMPTY) {
+            word = atomicCAS(reinterpret_cast<unsigned long long *>(&P.tab[sp.s].fp), 0ull, mine);
+            if (word != 0ull) continue;  // lost: the slot holds a fingerprint now, step on it
+          } else {  // STEP_CLAIM_TOMB
+            word = atomicCAS(reinterpret_cast<unsigned long long *>(&P.tab[sp.tomb].fp),
+                             (unsigned long long)kSlotTomb, mine);
+            if (word != kSlotTomb) {
+              slot_probe_lost_tomb(sp, fp, P.mask);  // resume at the slot it lost
+              continue;
+            }
+            sp.s = sp.tomb;
+          }
+          FlowHot &r = P.tab[sp.s];  // claimed: store the key (read by the verify launch)
+#pragma unroll
+          for (int j = 0; j < 10; j++) r.key[j] = k[j];
+          created = true;
+          break;
+        }
+        s = sp.s;
+      }
+    } else if (probes) {
       s = fp & P.mask;
       uint64_t probe = 0;
       for (; probe <= P.mask; probe++) {  // every lane leaves after at most capacity probes
@@ -550,11 +615,26 @@ __global__ __launch_bounds__(kFlowThreads) void flow_ids_scatter_kernel(const gp
   }
 }
 
+// The record of key k under fingerprint fp, or GPD_FLOW_NONE: the read-only probe of the peer
+// lookup below and of gpd_flow_expire's pairing.
+__device__ __forceinline__ uint32_t find_record(const FlowHot *tab, uint64_t mask, uint64_t fp,
+                                                const uint32_t (&k)[10]) {
+  uint64_t s = fp & mask;
+  for (uint64_t probe = 0; probe <= mask; probe++) {
+    const uint64_t old = tab[s].fp;
+    if (old == 0ull) break;
+    if ((old & kFpBits) == fp) return same_key(tab[s], k) ? (uint32_t)s : GPD_FLOW_NONE;
+    s = (s + 1) & mask;
+  }
+  return GPD_FLOW_NONE;
+}
+
 // The connection tracker's peer lookup (gpd_internal.h PeerArgs): one lane per tracked packet.
 // The probe is read-only and follows the insert's sequence for the reversed key's fingerprint: an
 // empty slot ends it (no record), the first slot with the fingerprint ends it (the insert
 // stops there too: a different key under that fingerprint is a collision, and its packets got no
-// record).  The loads that do not depend on the probe — the packet's flag byte, its own
+// record); a tombstone (gpd_flow_slots.h) is neither, since fingerprints are never 0, so the
+// probe walks past it.  The loads that do not depend on the probe — the packet's flag byte, its own
 // record's `first` and carried byte — are issued before it, and the peer's `first` and carried
 // byte together after it, ahead of the compare that picks the connection.
 __global__ __launch_bounds__(kFlowThreads) void flow_peer_kernel(FlowParams P, PeerArgs A) {
@@ -571,17 +651,7 @@ __global__ __launch_bounds__(kFlowThreads) void flow_peer_kernel(FlowParams P, P
     const uint32_t tf = fb < P.data_len ? P.data[fb] : 0u;
     const uint32_t rk[10] = {k[4], k[5], k[6], k[7], k[0], k[1], k[2], k[3], (k[8] >> 16) | (k[8] << 16), k[9]};
     const uint64_t fp = fingerprint(rk, P.fp_mask);
-    uint64_t s = fp & P.mask;
-    uint32_t r = GPD_FLOW_NONE;
-    for (uint64_t probe = 0; probe <= P.mask; probe++) {
-      const uint64_t old = P.tab[s].fp;
-      if (old == 0ull) break;
-      if ((old & kFpBits) == fp) {
-        if (same_key(P.tab[s], rk)) r = (uint32_t)s;
-        break;
-      }
-      s = (s + 1) & P.mask;
-    }
+    const uint32_t r = find_record(P.tab, P.mask, fp, rk);
     const uint32_t rr = r == GPD_FLOW_NONE ? f : r;
     const uint64_t first_r = P.cold[rr].first;
     const uint32_t carried_r = A.carried[rr];
@@ -612,7 +682,7 @@ __global__ __launch_bounds__(kFlowThreads) void flow_export_kernel(const FlowHot
   for (uint64_t s = blockIdx.x * (uint64_t)kFlowThreads + threadIdx.x; s < cap;
        s += (uint64_t)gridDim.x * kFlowThreads) {
     const FlowHot h = tab[s];
-    if (h.fp != 0) {
+    if ((h.fp & kFpBits) != 0) {  // (a tombstone's fingerprint bits are zero: not occupied)
       const unsigned long long j = atomicAdd(stats + stat_at(FS_EXPORT), 1ull);
       if (j < max) {
         const FlowCold c = cold[s];
@@ -635,6 +705,114 @@ __global__ __launch_bounds__(kFlowThreads) void flow_export_kernel(const FlowHot
   }
 }
 
+// ---- records that leave (include/gpd_flow_expire.h; slot rules in gpd_flow_slots.h) ----
+//
+// gpd_flow_expire marks, pairs, compacts and removes; gpd_flow_remove removes the ids it is
+// given; both end with the sweep.  All of it is ordered with the table's inserts on one stream,
+// so no kernel here runs beside a prober.
+struct ExpireArgs {
+  const FlowHot *tab;
+  uint64_t mask;        // capacity - 1
+  uint64_t last_below;  // candidates: last < last_below
+  const uint8_t *hold;  // a byte per record: non-zero keeps it (may be null)
+  const uint64_t *cand;  // the mark launch's bitmap (the pairs launch reads it)
+  uint64_t fp_mask;
+};
+
+// One lane per slot: an occupied record that is idle (strictly, as time.Before) and not held.
+__global__ __launch_bounds__(256) void flow_expire_mark_kernel(ExpireArgs A, uint64_t *bits, uint32_t *blk) {
+  compact_count((uint32_t)(A.mask + 1ull), bits, blk, [&](uint32_t s) {
+    const uint64_t word = A.tab[s].fp;
+    return slot_kind(word) == SLOT_USED && A.tab[s].last < A.last_below && !(A.hold && A.hold[s]);
+  });
+}
+
+// GPD_FLOW_EXPIRE_PAIRS, a launch of its own so that every candidate bit is visible: a candidate
+// stays one only if the record of its reversed key is a candidate too.  No such record, or the
+// record itself (a key that is its own reverse), is a complete pair.
+__global__ __launch_bounds__(256) void flow_expire_pairs_kernel(ExpireArgs A, uint64_t *bits, uint32_t *blk) {
+  compact_count((uint32_t)(A.mask + 1ull), bits, blk, [&](uint32_t s) {
+    if (!((A.cand[s >> 6] >> (s & 63u)) & 1ull)) return false;
+    const uint32_t *k = A.tab[s].key;
+    const uint32_t rk[10] = {k[4], k[5], k[6], k[7], k[0], k[1], k[2], k[3], (k[8] >> 16) | (k[8] << 16), k[9]};
+    const uint32_t r = find_record(A.tab, A.mask, fingerprint(rk, A.fp_mask), rk);
+    return r == GPD_FLOW_NONE || r == s || ((A.cand[r >> 6] >> (r & 63u)) & 1ull) != 0ull;
+  });
+}
+
+__global__ __launch_bounds__(1024) void flow_expire_scan_kernel(uint32_t *blk, uint32_t nblk) {
+  compact_scan(blk, nblk);
+}
+
+// The marked slots' indices, ascending: they are the removed ids.
+__global__ __launch_bounds__(64) void flow_expire_index_kernel(const uint32_t *blk, const uint64_t *bits,
+                                                               uint32_t *ids, uint32_t cap) {
+  compact_index(blk, bits, ids, cap);
+}
+
+// StreamPool.remove: one lane per id.  The compare-and-swap fingerprint -> tombstone has one
+// winner among duplicates; the winner returns the rest of the slot to what flow_reset_kernel
+// writes, so a later owner's `first` starts from ~0 again.
+__global__ __launch_bounds__(kFlowThreads) void flow_remove_kernel(FlowHot *tab, FlowCold *cold, uint64_t cap,
+                                                                  const uint32_t *ids, uint64_t m,
+                                                                  unsigned long long *stats) {
+  unsigned long long t_gone = 0;
+  for (uint64_t j = blockIdx.x * (uint64_t)kFlowThreads + threadIdx.x; j - threadIdx.x < m;
+       j += (uint64_t)gridDim.x * kFlowThreads) {
+    bool won = false;
+    const uint64_t id = j < m ? ids[j] : ~0ull;
+    if (id < cap) {
+      const unsigned long long old = *reinterpret_cast<volatile unsigned long long *>(&tab[id].fp);
+      if (slot_kind(old) == SLOT_USED)
+        won = atomicCAS(reinterpret_cast<unsigned long long *>(&tab[id].fp), old, (unsigned long long)kSlotTomb) == old;
+      if (won) {
+        FlowHot &r = tab[id];
+#pragma unroll
+        for (int w = 0; w < 10; w++) r.key[w] = 0u;
+        r.cnt = 0ull;
+        r.last = 0ull;
+        cold[id] = FlowCold{~0ull, 0ull};
+      }
+    }
+    wave_tally(t_gone, won);
+  }
+  wave_flush(stats + stat_at(FS_FLOWS), 0ull - t_gone);  // (flows -= removed, as one wrapped add)
+}
+
+// The sweep (slot_sweep_at): one lane per slot; the lane of an empty slot behind a tombstone
+// clears the run that ends there.  A lane's serial work is its run's length, which is a
+// cluster's: short at the loads a table is run at.  When no record is left every
+// tombstone goes, whether an empty slot bounds its run or not (a table that was full), and the
+// slots equal a reset table's.
+__global__ __launch_bounds__(kFlowThreads) void flow_sweep_kernel(FlowHot *tab, uint64_t cap,
+                                                                 const unsigned long long *stats) {
+  const bool none_left = stats[stat_at(FS_FLOWS)] == 0ull;
+  auto word_at = [&](uint64_t i) { return (uint64_t) * reinterpret_cast<volatile unsigned long long *>(&tab[i].fp); };
+  auto clear = [&](uint64_t i) { *reinterpret_cast<volatile unsigned long long *>(&tab[i].fp) = 0ull; };
+  for (uint64_t s = blockIdx.x * (uint64_t)kFlowThreads + threadIdx.x; s < cap;
+       s += (uint64_t)gridDim.x * kFlowThreads) {
+    if (none_left) {
+      if (slot_kind(word_at(s)) == SLOT_TOMB) clear(s);
+    } else {
+      (void)slot_sweep_at(word_at, clear, cap - 1ull, s);
+    }
+  }
+}
+
+// gpd_flow_load: records in use and tombstones, counted.
+__global__ __launch_bounds__(kFlowThreads) void flow_load_kernel(const FlowHot *tab, uint64_t cap,
+                                                                unsigned long long *stats) {
+  unsigned long long t_used = 0, t_tomb = 0;
+  for (uint64_t s = blockIdx.x * (uint64_t)kFlowThreads + threadIdx.x; s - threadIdx.x < cap;
+       s += (uint64_t)gridDim.x * kFlowThreads) {
+    const SlotKind kind = s < cap ? slot_kind(tab[s].fp) : SLOT_EMPTY;
+    wave_tally(t_used, kind == SLOT_USED);
+    wave_tally(t_tomb, kind == SLOT_TOMB);
+  }
+  wave_flush(stats + stat_at(FS_LOAD_USED), t_used);
+  wave_flush(stats + stat_at(FS_LOAD_TOMB), t_tomb);
+}
+
 }  // namespace gpd
 
 struct gpd_flowtable {
@@ -653,6 +831,11 @@ struct gpd_flowtable {
   uint32_t epoch = 0;                 // insert launches so far, mod 255
   uint64_t seen = 0;                  // FlowParams::seen, while seen_known
   bool seen_known = true;             // false after key records went in (until a reset)
+  // gpd_flow_expire.h: the table may hold tombstones (set by a removal, cleared by a reset and by
+  // a gpd_flow_load that counts none); while set, inserts run the TOMBS kernels
+  bool may_tomb = false;
+  uint64_t *ex_bits = nullptr;  // gpd_flow_expire: two bitmaps of cap bits (marked, paired)
+  uint32_t *ex_blk = nullptr;   // and the compaction's block counts (+ the total)
 };
 
 // The next insert launch's epoch tag (1..255 in the fingerprint word's top byte).
@@ -785,6 +968,7 @@ int gpd_flow_reset(gpd_flowtable *ft, void *stream) {
   FLOW_TRY(hipMemsetAsync(ft->stats, 0, gpd::stat_at(gpd::FS_WORDS) * sizeof(unsigned long long), s));
   ft->seen = 0;
   ft->seen_known = true;
+  ft->may_tomb = false;
   return GPD_OK;
 }
 
@@ -814,7 +998,8 @@ int gpd_flow_insert(gpd_flowtable *ft, const gpd_batch *in, const gpd_result *re
   ft->seen = std::max(ft->seen, top);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(grid_for(in->n, ft->num_cus)), block(gpd::kFlowThreads);
-  hipLaunchKernelGGL(gpd::flow_insert_kernel<false>, grid, block, 0, s, P);
+  if (ft->may_tomb) hipLaunchKernelGGL((gpd::flow_insert_kernel<false, true>), grid, block, 0, s, P);
+  else hipLaunchKernelGGL((gpd::flow_insert_kernel<false, false>), grid, block, 0, s, P);
   FLOW_TRY(hipGetLastError());
   hipLaunchKernelGGL(gpd::flow_verify_kernel<false>, grid, block, 0, s, P);
   FLOW_TRY(hipGetLastError());
@@ -903,7 +1088,8 @@ int gpd_flow_insert_keys(gpd_flowtable *ft, const gpd_flow_key *keys, uint64_t n
   ft->seen_known = false;  // (P.seen stays ~0: the key records' sequence numbers are unknown here)
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(grid_for(n, ft->num_cus)), block(gpd::kFlowThreads);
-  hipLaunchKernelGGL(gpd::flow_insert_kernel<true>, grid, block, 0, s, P);
+  if (ft->may_tomb) hipLaunchKernelGGL((gpd::flow_insert_kernel<true, true>), grid, block, 0, s, P);
+  else hipLaunchKernelGGL((gpd::flow_insert_kernel<true, false>), grid, block, 0, s, P);
   FLOW_TRY(hipGetLastError());
   hipLaunchKernelGGL(gpd::flow_verify_kernel<true>, grid, block, 0, s, P);
   FLOW_TRY(hipGetLastError());
@@ -971,6 +1157,94 @@ int gpd_flow_export(gpd_flowtable *ft, gpd_flow_rec *out, uint32_t *rec_index, u
   return GPD_OK;
 }
 
+// ---- include/gpd_flow_expire.h ----
+
+// The removal of ids[0, m) and the sweep behind it (both asynchronous).
+static int remove_and_sweep(gpd_flowtable *ft, const uint32_t *ids, uint64_t m, hipStream_t s) {
+  hipLaunchKernelGGL(gpd::flow_remove_kernel, dim3(grid_for(m, ft->num_cus)), dim3(gpd::kFlowThreads), 0, s,
+                     ft->tab, ft->cold, ft->cap, ids, m, ft->stats);
+  FLOW_TRY(hipGetLastError());
+  ft->may_tomb = true;
+  hipLaunchKernelGGL(gpd::flow_sweep_kernel, dim3(grid_for(ft->cap, ft->num_cus)), dim3(gpd::kFlowThreads), 0, s,
+                     ft->tab, ft->cap, ft->stats);
+  FLOW_TRY(hipGetLastError());
+  return GPD_OK;
+}
+
+int gpd_flow_remove(gpd_flowtable *ft, const uint32_t *ids, uint64_t m, void *stream) {
+  if (!ft || (m && !ids)) return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_remove: null argument");
+  if (m == 0) return GPD_OK;
+  gpd::DeviceScope dscope_;
+  FLOW_TRY(dscope_.set(ft->device));
+  return remove_and_sweep(ft, ids, m, (hipStream_t)stream);
+}
+
+int gpd_flow_expire(gpd_flowtable *ft, uint64_t last_below, const uint8_t *hold, uint32_t flags,
+                    uint32_t *ids, uint64_t max_ids, uint64_t *count, void *stream) {
+  if (!ft || !count) return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_expire: null argument");
+  *count = 0;
+  if (flags & ~GPD_FLOW_EXPIRE_PAIRS)
+    return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_expire: unknown flags 0x%x", flags);
+  if (!ids && max_ids)
+    return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_expire: null ids with max_ids %llu",
+                          (unsigned long long)max_ids);
+  if (last_below == 0) return GPD_OK;  // (nothing is before the first packet)
+  gpd::DeviceScope dscope_;
+  FLOW_TRY(dscope_.set(ft->device));
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t words = (ft->cap + 63) / 64;
+  const uint32_t nblk = (uint32_t)((ft->cap + gpd::kCompactBlock - 1) / gpd::kCompactBlock);
+  if (!ft->ex_bits) FLOW_TRY(hipMalloc(&ft->ex_bits, 2 * words * sizeof(uint64_t)));
+  if (!ft->ex_blk) FLOW_TRY(hipMalloc(&ft->ex_blk, ((uint64_t)nblk + 1) * sizeof(uint32_t)));
+  gpd::ExpireArgs A{ft->tab, ft->cap - 1, last_below, hold, ft->ex_bits, ft->fp_mask};
+  uint64_t *bits = ft->ex_bits;
+  hipLaunchKernelGGL(gpd::flow_expire_mark_kernel, dim3(nblk), dim3(256), 0, s, A, bits, ft->ex_blk);
+  FLOW_TRY(hipGetLastError());
+  if (flags & GPD_FLOW_EXPIRE_PAIRS) {
+    bits = ft->ex_bits + words;
+    hipLaunchKernelGGL(gpd::flow_expire_pairs_kernel, dim3(nblk), dim3(256), 0, s, A, bits, ft->ex_blk);
+    FLOW_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(gpd::flow_expire_scan_kernel, dim3(1), dim3(1024), 0, s, ft->ex_blk, nblk);
+  FLOW_TRY(hipGetLastError());
+  uint32_t total = 0;
+  FLOW_TRY(hipMemcpyAsync(&total, ft->ex_blk + nblk, sizeof total, hipMemcpyDeviceToHost, s));
+  FLOW_TRY(hipStreamSynchronize(s));
+  *count = total;
+  if (!ids && max_ids == 0) return GPD_OK;  // the sizing call
+  if (total > max_ids)
+    return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_expire: %u records to remove, room for %llu ids", total,
+                          (unsigned long long)max_ids);
+  if (total == 0) return GPD_OK;
+  hipLaunchKernelGGL(gpd::flow_expire_index_kernel, dim3(nblk), dim3(64), 0, s, ft->ex_blk, bits, ids,
+                     (uint32_t)ft->cap);
+  FLOW_TRY(hipGetLastError());
+  const int rc = remove_and_sweep(ft, ids, total, s);
+  if (rc != GPD_OK) return rc;
+  FLOW_TRY(hipStreamSynchronize(s));
+  return GPD_OK;
+}
+
+int gpd_flow_load(gpd_flowtable *ft, uint64_t out[2], void *stream) {
+  if (!ft || !out) return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_load: null argument");
+  gpd::DeviceScope dscope_;
+  FLOW_TRY(dscope_.set(ft->device));
+  hipStream_t s = (hipStream_t)stream;
+  unsigned long long *w = ft->stats + gpd::stat_at(gpd::FS_LOAD_USED);
+  static_assert(gpd::FS_LOAD_TOMB == gpd::FS_LOAD_USED + 1, "one clear and one copy for both words");
+  FLOW_TRY(hipMemsetAsync(w, 0, (gpd::kStatStride + 1) * sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(gpd::flow_load_kernel, dim3(grid_for(ft->cap, ft->num_cus)), dim3(gpd::kFlowThreads), 0, s,
+                     ft->tab, ft->cap, ft->stats);
+  FLOW_TRY(hipGetLastError());
+  unsigned long long h[gpd::kStatStride + 1];
+  FLOW_TRY(hipMemcpyAsync(h, w, sizeof h, hipMemcpyDeviceToHost, s));
+  FLOW_TRY(hipStreamSynchronize(s));
+  out[0] = h[0];
+  out[1] = h[gpd::kStatStride];
+  if (out[1] == 0) ft->may_tomb = false;  // (calls on a table are ordered: none can appear unseen)
+  return GPD_OK;
+}
+
 int gpd_flow_test_fingerprint_bits(gpd_flowtable *ft, uint32_t bits) {
   if (!ft || bits == 0 || bits > 64)
     return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_test_fingerprint_bits: bits %u outside [1, 64]", bits);
@@ -994,6 +1268,8 @@ int gpd_flow_destroy(gpd_flowtable *ft) {
   if (ft->stats) (void)hipFree(ft->stats);
   if (ft->parts) (void)hipFree(ft->parts);
   if (ft->made) (void)hipFree(ft->made);
+  if (ft->ex_bits) (void)hipFree(ft->ex_bits);
+  if (ft->ex_blk) (void)hipFree(ft->ex_blk);
   delete ft;
   return GPD_OK;
 }

@@ -39,8 +39,10 @@
  * Out of scope:
  *   - TCPOptionCheck.Accept (tcpcheck.go:47-106): it needs half.nextSeq, the assembler's;
  *   - AssembleWithContext itself (ordering, buffering, ScatterGather delivery);
- *   - expiry by time (FlushCloseOlderThan): connections leave through _forget and _reset only —
- *     TCPStateReset is terminal in the reference, too;
+ *   - expiry by time (FlushCloseOlderThan) is the flow table's: gpd_flow_expire (gpd_flow_expire.h)
+ *     removes idle records, a connection's two halves together, and its ids go to _forget here;
+ *     within the tracker connections leave through _forget and _reset only — TCPStateReset is
+ *     terminal in the reference, too;
  *   - tables filled through gpd_flow_insert_keys (sharding): their `first` words are the senders'.
  *
  * Reference interfaces the entry points replace (paths relative to google/gopacket):
