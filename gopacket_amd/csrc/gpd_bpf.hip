@@ -131,13 +131,6 @@ __global__ __launch_bounds__(kBpfThreads) void bpf_kernel(BpfArgs A, const uint2
   }
 }
 
-#define BPF_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-  } while (0)
-
 }  // namespace
 }  // namespace gpd
 
@@ -152,7 +145,7 @@ int gpd_bpf_create(gpd_ctx *ctx, const gpd_bpf_insn *prog, uint32_t len, gpd_bpf
   const int rc = bpf_validate(who, prog, len, &uses_mem);
   if (rc) return rc;
   DeviceScope dscope_;
-  BPF_TRY(dscope_.set(ctx_device(ctx)));
+  GPD_TRY(dscope_.set(ctx_device(ctx)));
   uint2 *d = nullptr;
   const hipError_t e = hipMalloc(reinterpret_cast<void **>(&d), (size_t)len * sizeof(gpd_bpf_insn));
   if (e != hipSuccess)
@@ -189,7 +182,7 @@ int gpd_bpf_filter(gpd_bpf *f, const gpd_batch *in, const uint32_t *wirelen, uin
                      (unsigned long long)in->data_len);
   if (!keep) return set_error(GPD_ERR_INVALID, "%s: null keep", who);
   DeviceScope dscope_;
-  BPF_TRY(dscope_.set(f->device));
+  GPD_TRY(dscope_.set(f->device));
   BpfArgs A{};
   A.data = in->data;
   A.dlen = (uint32_t)in->data_len;
@@ -210,7 +203,7 @@ int gpd_bpf_filter(gpd_bpf *f, const gpd_batch *in, const uint32_t *wirelen, uin
     hipLaunchKernelGGL(bpf_kernel<true>, dim3((unsigned)g.blocks), dim3(kBpfThreads), 0, s, A, f->prog);
   else
     hipLaunchKernelGGL(bpf_kernel<false>, dim3((unsigned)g.blocks), dim3(kBpfThreads), 0, s, A, f->prog);
-  BPF_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   return GPD_OK;
 }
 

@@ -844,13 +844,6 @@ static uint64_t next_tag(gpd_flowtable *ft) {
   return (uint64_t)ft->epoch << 56;
 }
 
-#define FLOW_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));          \
-  } while (0)
-
 static unsigned grid_for(uint64_t work, int num_cus) {
   const uint64_t blocks = (work + gpd::kFlowThreads - 1) / gpd::kFlowThreads;
   return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)num_cus * 8));
@@ -914,14 +907,14 @@ int gpd_fast_hash(int device, uint64_t n, const int64_t *typ, const uint8_t *src
   if (((uintptr_t)src | (uintptr_t)(dst ? dst : src)) & 15u)
     return gpd::set_error(GPD_ERR_INVALID, "gpd_fast_hash: raw arrays must be 16-byte aligned");
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(device));
+  GPD_TRY(dscope_.set(device));
   int cus = 0;
-  FLOW_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  GPD_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
   const uint64_t blocks = std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(cus, 1) * 8);
   hipLaunchKernelGGL(fast_hash_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, typ,
                      reinterpret_cast<const uint4 *>(src), src_len, reinterpret_cast<const uint4 *>(dst),
                      dst_len, out);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   return GPD_OK;
 }
 
@@ -960,12 +953,12 @@ int gpd_flow_create(gpd_ctx *ctx, uint64_t capacity, gpd_flowtable **out) {
 int gpd_flow_reset(gpd_flowtable *ft, void *stream) {
   if (!ft) return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_reset: null table");
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(ft->device));
+  GPD_TRY(dscope_.set(ft->device));
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(gpd::flow_reset_kernel, dim3(grid_for(ft->cap, ft->num_cus)),
                      dim3(gpd::kFlowThreads), 0, s, ft->tab, ft->cold, ft->cap);
-  FLOW_TRY(hipGetLastError());
-  FLOW_TRY(hipMemsetAsync(ft->stats, 0, gpd::stat_at(gpd::FS_WORDS) * sizeof(unsigned long long), s));
+  GPD_TRY(hipGetLastError());
+  GPD_TRY(hipMemsetAsync(ft->stats, 0, gpd::stat_at(gpd::FS_WORDS) * sizeof(unsigned long long), s));
   ft->seen = 0;
   ft->seen_known = true;
   ft->may_tomb = false;
@@ -982,11 +975,11 @@ int gpd_flow_insert(gpd_flowtable *ft, const gpd_batch *in, const gpd_result *re
   if (!in->data || !in->offset || !in->caplen)
     return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_insert: null batch array");
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(ft->device));
+  GPD_TRY(dscope_.set(ft->device));
   gpd::FlowParams P{in->data, in->data_len, in->offset, in->caplen, res->status, res->hdr_off,
                     flow_id, in->n, index_base, ft->tab, ft->cap - 1, ft->stats,
                     nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-  FLOW_TRY(grow_made(ft, in->n));
+  GPD_TRY(grow_made(ft, in->n));
   P.made = ft->made;
   P.fp_mask = ft->fp_mask;
   P.rec = res->records;
@@ -1000,9 +993,9 @@ int gpd_flow_insert(gpd_flowtable *ft, const gpd_batch *in, const gpd_result *re
   const dim3 grid(grid_for(in->n, ft->num_cus)), block(gpd::kFlowThreads);
   if (ft->may_tomb) hipLaunchKernelGGL((gpd::flow_insert_kernel<false, true>), grid, block, 0, s, P);
   else hipLaunchKernelGGL((gpd::flow_insert_kernel<false, false>), grid, block, 0, s, P);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   hipLaunchKernelGGL(gpd::flow_verify_kernel<false>, grid, block, 0, s, P);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   return GPD_OK;
 }
 
@@ -1021,15 +1014,15 @@ int gpd_flow_keys(gpd_flowtable *ft, const gpd_batch *in, const gpd_result *res,
   if (!in->data || !in->offset || !in->caplen)
     return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_keys: null batch array");
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(ft->device));
+  GPD_TRY(dscope_.set(ft->device));
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(grid_for(in->n, ft->num_cus)), block(gpd::kFlowThreads);
   const uint64_t L = (uint64_t)nparts * grid.x, words = L + 1 + nparts;
   if (ft->parts_words < words) {
-    if (ft->parts) FLOW_TRY(hipFree(ft->parts));
+    if (ft->parts) GPD_TRY(hipFree(ft->parts));
     ft->parts = nullptr;
     ft->parts_words = 0;
-    FLOW_TRY(hipMalloc(&ft->parts, words * sizeof(unsigned long long)));
+    GPD_TRY(hipMalloc(&ft->parts, words * sizeof(unsigned long long)));
     ft->parts_words = words;
   }
   gpd::FlowParams P{in->data, in->data_len, in->offset, in->caplen, res->status, res->hdr_off,
@@ -1038,15 +1031,15 @@ int gpd_flow_keys(gpd_flowtable *ft, const gpd_batch *in, const gpd_result *res,
   P.fp_mask = ft->fp_mask;
   P.rec = res->records;
   hipLaunchKernelGGL(gpd::flow_part_count_kernel, grid, block, 0, s, P);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   hipLaunchKernelGGL(gpd::flow_part_scan_kernel, dim3(1), dim3(1024), 0, s, ft->parts, L, nparts, grid.x);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   hipLaunchKernelGGL(gpd::flow_part_scatter_kernel, grid, block, 0, s, P);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   std::vector<unsigned long long> h(nparts);
-  FLOW_TRY(hipMemcpyAsync(h.data(), ft->parts + L + 1, nparts * sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost, s));
-  FLOW_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(h.data(), ft->parts + L + 1, nparts * sizeof(unsigned long long),
+                         hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   for (uint32_t p = 0; p < nparts; p++) part_count[p] = h[p];
   return GPD_OK;
 }
@@ -1057,15 +1050,15 @@ int gpd_flow_key_ids(gpd_flowtable *ft, const gpd_flow_key *keys, uint64_t m, co
     return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_key_ids: null argument");
   if (n == 0) return GPD_OK;
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(ft->device));
+  GPD_TRY(dscope_.set(ft->device));
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(gpd::flow_ids_fill_kernel, dim3(grid_for(n, ft->num_cus)), dim3(gpd::kFlowThreads),
                      0, s, owner, flow_id, n);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   if (m) {
     hipLaunchKernelGGL(gpd::flow_ids_scatter_kernel, dim3(grid_for(m, ft->num_cus)),
                        dim3(gpd::kFlowThreads), 0, s, keys, m, ids, index_base, n, owner, flow_id);
-    FLOW_TRY(hipGetLastError());
+    GPD_TRY(hipGetLastError());
   }
   return GPD_OK;
 }
@@ -1076,10 +1069,10 @@ int gpd_flow_insert_keys(gpd_flowtable *ft, const gpd_flow_key *keys, uint64_t n
     return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_insert_keys: null argument");
   if (n == 0) return GPD_OK;
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(ft->device));
+  GPD_TRY(dscope_.set(ft->device));
   gpd::FlowParams P{nullptr, 0, nullptr, nullptr, nullptr, nullptr, flow_id, n, 0, ft->tab,
                     ft->cap - 1, ft->stats, keys, nullptr, nullptr, nullptr, nullptr, 0};
-  FLOW_TRY(grow_made(ft, n));
+  GPD_TRY(grow_made(ft, n));
   P.made = ft->made;
   P.fp_mask = ft->fp_mask;  // (key records carry their sender's fingerprint; recomputed here)
   P.cbits = ft->cbits;
@@ -1090,19 +1083,19 @@ int gpd_flow_insert_keys(gpd_flowtable *ft, const gpd_flow_key *keys, uint64_t n
   const dim3 grid(grid_for(n, ft->num_cus)), block(gpd::kFlowThreads);
   if (ft->may_tomb) hipLaunchKernelGGL((gpd::flow_insert_kernel<true, true>), grid, block, 0, s, P);
   else hipLaunchKernelGGL((gpd::flow_insert_kernel<true, false>), grid, block, 0, s, P);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   hipLaunchKernelGGL(gpd::flow_verify_kernel<true>, grid, block, 0, s, P);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   return GPD_OK;
 }
 
 int gpd_flow_stats_get(gpd_flowtable *ft, gpd_flow_stats *out, void *stream) {
   if (!ft || !out) return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_stats_get: null argument");
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(ft->device));
+  GPD_TRY(dscope_.set(ft->device));
   unsigned long long hs[gpd::stat_at(gpd::FS_WORDS)], h[gpd::FS_WORDS];
-  FLOW_TRY(hipMemcpyAsync(hs, ft->stats, sizeof hs, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  FLOW_TRY(hipStreamSynchronize((hipStream_t)stream));
+  GPD_TRY(hipMemcpyAsync(hs, ft->stats, sizeof hs, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  GPD_TRY(hipStreamSynchronize((hipStream_t)stream));
   for (uint32_t w = 0; w < gpd::FS_WORDS; w++) h[w] = hs[gpd::stat_at(w)];
   out->flows = h[gpd::FS_FLOWS];
   out->packets = h[gpd::FS_PACKETS];
@@ -1118,7 +1111,7 @@ int gpd_flow_export(gpd_flowtable *ft, gpd_flow_rec *out, uint32_t *rec_index, u
   if (!ft || !out || !n) return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_export: null argument");
   *n = 0;
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(ft->device));
+  GPD_TRY(dscope_.set(ft->device));
   hipStream_t s = (hipStream_t)stream;
   gpd_flow_stats st;
   int rc = gpd_flow_stats_get(ft, &st, stream);
@@ -1127,7 +1120,7 @@ int gpd_flow_export(gpd_flowtable *ft, gpd_flow_rec *out, uint32_t *rec_index, u
   if (m == 0) return GPD_OK;
   gpd_flow_rec *d_out = nullptr;
   uint32_t *d_idx = nullptr;
-  FLOW_TRY(hipMalloc(&d_out, m * sizeof(gpd_flow_rec)));
+  GPD_TRY(hipMalloc(&d_out, m * sizeof(gpd_flow_rec)));
   hipError_t e = hipMalloc(&d_idx, m * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemsetAsync(ft->stats + gpd::stat_at(gpd::FS_EXPORT), 0, sizeof(unsigned long long), s);
   if (e == hipSuccess) {
@@ -1163,11 +1156,11 @@ int gpd_flow_export(gpd_flowtable *ft, gpd_flow_rec *out, uint32_t *rec_index, u
 static int remove_and_sweep(gpd_flowtable *ft, const uint32_t *ids, uint64_t m, hipStream_t s) {
   hipLaunchKernelGGL(gpd::flow_remove_kernel, dim3(grid_for(m, ft->num_cus)), dim3(gpd::kFlowThreads), 0, s,
                      ft->tab, ft->cold, ft->cap, ids, m, ft->stats);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   ft->may_tomb = true;
   hipLaunchKernelGGL(gpd::flow_sweep_kernel, dim3(grid_for(ft->cap, ft->num_cus)), dim3(gpd::kFlowThreads), 0, s,
                      ft->tab, ft->cap, ft->stats);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   return GPD_OK;
 }
 
@@ -1175,7 +1168,7 @@ int gpd_flow_remove(gpd_flowtable *ft, const uint32_t *ids, uint64_t m, void *st
   if (!ft || (m && !ids)) return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_remove: null argument");
   if (m == 0) return GPD_OK;
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(ft->device));
+  GPD_TRY(dscope_.set(ft->device));
   return remove_and_sweep(ft, ids, m, (hipStream_t)stream);
 }
 
@@ -1190,26 +1183,26 @@ int gpd_flow_expire(gpd_flowtable *ft, uint64_t last_below, const uint8_t *hold,
                           (unsigned long long)max_ids);
   if (last_below == 0) return GPD_OK;  // (nothing is before the first packet)
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(ft->device));
+  GPD_TRY(dscope_.set(ft->device));
   hipStream_t s = (hipStream_t)stream;
   const uint64_t words = (ft->cap + 63) / 64;
   const uint32_t nblk = (uint32_t)((ft->cap + gpd::kCompactBlock - 1) / gpd::kCompactBlock);
-  if (!ft->ex_bits) FLOW_TRY(hipMalloc(&ft->ex_bits, 2 * words * sizeof(uint64_t)));
-  if (!ft->ex_blk) FLOW_TRY(hipMalloc(&ft->ex_blk, ((uint64_t)nblk + 1) * sizeof(uint32_t)));
+  if (!ft->ex_bits) GPD_TRY(hipMalloc(&ft->ex_bits, 2 * words * sizeof(uint64_t)));
+  if (!ft->ex_blk) GPD_TRY(hipMalloc(&ft->ex_blk, ((uint64_t)nblk + 1) * sizeof(uint32_t)));
   gpd::ExpireArgs A{ft->tab, ft->cap - 1, last_below, hold, ft->ex_bits, ft->fp_mask};
   uint64_t *bits = ft->ex_bits;
   hipLaunchKernelGGL(gpd::flow_expire_mark_kernel, dim3(nblk), dim3(256), 0, s, A, bits, ft->ex_blk);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   if (flags & GPD_FLOW_EXPIRE_PAIRS) {
     bits = ft->ex_bits + words;
     hipLaunchKernelGGL(gpd::flow_expire_pairs_kernel, dim3(nblk), dim3(256), 0, s, A, bits, ft->ex_blk);
-    FLOW_TRY(hipGetLastError());
+    GPD_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(gpd::flow_expire_scan_kernel, dim3(1), dim3(1024), 0, s, ft->ex_blk, nblk);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint32_t total = 0;
-  FLOW_TRY(hipMemcpyAsync(&total, ft->ex_blk + nblk, sizeof total, hipMemcpyDeviceToHost, s));
-  FLOW_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(&total, ft->ex_blk + nblk, sizeof total, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   *count = total;
   if (!ids && max_ids == 0) return GPD_OK;  // the sizing call
   if (total > max_ids)
@@ -1218,27 +1211,27 @@ int gpd_flow_expire(gpd_flowtable *ft, uint64_t last_below, const uint8_t *hold,
   if (total == 0) return GPD_OK;
   hipLaunchKernelGGL(gpd::flow_expire_index_kernel, dim3(nblk), dim3(64), 0, s, ft->ex_blk, bits, ids,
                      (uint32_t)ft->cap);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   const int rc = remove_and_sweep(ft, ids, total, s);
   if (rc != GPD_OK) return rc;
-  FLOW_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipStreamSynchronize(s));
   return GPD_OK;
 }
 
 int gpd_flow_load(gpd_flowtable *ft, uint64_t out[2], void *stream) {
   if (!ft || !out) return gpd::set_error(GPD_ERR_INVALID, "gpd_flow_load: null argument");
   gpd::DeviceScope dscope_;
-  FLOW_TRY(dscope_.set(ft->device));
+  GPD_TRY(dscope_.set(ft->device));
   hipStream_t s = (hipStream_t)stream;
   unsigned long long *w = ft->stats + gpd::stat_at(gpd::FS_LOAD_USED);
   static_assert(gpd::FS_LOAD_TOMB == gpd::FS_LOAD_USED + 1, "one clear and one copy for both words");
-  FLOW_TRY(hipMemsetAsync(w, 0, (gpd::kStatStride + 1) * sizeof(unsigned long long), s));
+  GPD_TRY(hipMemsetAsync(w, 0, (gpd::kStatStride + 1) * sizeof(unsigned long long), s));
   hipLaunchKernelGGL(gpd::flow_load_kernel, dim3(grid_for(ft->cap, ft->num_cus)), dim3(gpd::kFlowThreads), 0, s,
                      ft->tab, ft->cap, ft->stats);
-  FLOW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   unsigned long long h[gpd::kStatStride + 1];
-  FLOW_TRY(hipMemcpyAsync(h, w, sizeof h, hipMemcpyDeviceToHost, s));
-  FLOW_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(h, w, sizeof h, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   out[0] = h[0];
   out[1] = h[gpd::kStatStride];
   if (out[1] == 0) ft->may_tomb = false;  // (calls on a table are ordered: none can appear unseen)

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "../../include/gpd.h"
 
 namespace gpd {
@@ -255,6 +257,33 @@ hipError_t launch_fast_sp(KParams &P, hipStream_t stream, int num_cus);
 
 // Host side: set the thread's gpd_last_error_string() text and return `code` (gpd_runtime.cpp).
 int set_error(int code, const char *fmt, ...);
+
+// Host side, the stage files' entry points: a failed HIP call ends the entry point with
+// GPD_ERR_HIP and the text "<the call as written>: <HIP's error string>".  (The context's files
+// have HIP_TRY, gpd_ctx.h, whose text differs.)
+#define GPD_TRY(expr)                                                                       \
+  do {                                                                                      \
+    hipError_t e_ = (expr);                                                                 \
+    if (e_ != hipSuccess)                                                                   \
+      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
+  } while (0)
+
+// Host side: a size rounded up to the 16 bytes the scratch carves and the vector loads need.
+inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+
+// Host side: device memory of at least `bytes` at *p (grown by replacement: the old contents
+// are not kept).
+template <class T>
+bool grow(T **p, size_t *cap, size_t bytes) {
+  if (*cap >= bytes && *p) return true;
+  const size_t want = std::max(bytes + bytes / 2, (size_t)4096);
+  void *q = nullptr;
+  if (hipMalloc(&q, want) != hipSuccess) return false;
+  if (*p) (void)hipFree(*p);
+  *p = static_cast<T *>(q);
+  *cap = want;
+  return true;
+}
 
 // Host side: the device and compute-unit count of a context (gpd_runtime.cpp).
 int ctx_device(const gpd_ctx *ctx);

@@ -11,9 +11,10 @@
 //                      index and compared through that item's key bytes, never through a hash
 //                      value; atomicMin keeps the key's first item
 //   ir_pair_kernel     (first item of the key, item) pairs
-//   is_hist / is_scan / is_scatter   the stable LSD radix sort of the pairs, 8 bits a pass (the
-//                      scheme of gpd_tcpseg.hip): groups in order of first appearance, each in
-//                      packet order, a carried list ahead of its key's records
+//   sort_hist / sort_scan / sort_scatter   the shared stable LSD radix sort of the pairs, 8 bits
+//                      a pass (gpd_radix_sort.h; the last pass's sink writes order[] and skey[]):
+//                      groups in order of first appearance, each in packet order, a carried list
+//                      ahead of its key's records
 //   ir_head / scan / index   the groups' first positions (gpd_compact.h)
 //   ir_wsum / scan / wapply  a group's private node and piece region: its carried nodes plus
 //                      its records bound both
@@ -27,9 +28,9 @@
 //                      dense places in output order
 //   ir_carry_kernel    one wave per group with a list left: the new list record, its nodes and
 //                      the pieces that copy their payloads into the new byte store
-//   ir_gather_kernel   the bandwidth path (twice: datagram bytes, the new store): a wave per 64
-//                      consecutive pieces, 16-byte output chunks from aligned source loads
-//                      shifted together, a source base per piece
+//   gather_kernel      the shared bandwidth path (gpd_gather.h; twice: the new store, datagram
+//                      bytes): a wave per 64 consecutive pieces, 16-byte output chunks from
+//                      aligned source loads shifted together, a source base per piece
 //   ir_patch_kernel    one lane per datagram: total length, flags/offset, header checksum
 #include <hip/hip_runtime.h>
 
@@ -37,8 +38,10 @@
 #include <new>
 
 #include "gpd_compact.h"
+#include "gpd_gather.h"
 #include "gpd_internal.h"
 #include "gpd_ip4reasm_walk.h"
+#include "gpd_radix_sort.h"
 #include "gpd_stream_util.h"
 
 // One key's list between batches (48 B).
@@ -79,13 +82,7 @@ static_assert(sizeof(gpd_ip4_outcome) == 8 && sizeof(gpd_ip4_dgram) == 32 && siz
 
 constexpr uint32_t kLrFinal = 1, kLrDead = 2;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr uint32_t kWalkWaves = 4;    // waves (groups) per walk / pieces / carry workgroup
-constexpr uint32_t kGatherWaves = 4;  // waves per gather workgroup
-constexpr uint32_t kSortThreads = 1024;
-constexpr uint32_t kSortWaves = kSortThreads / 64u;
-constexpr uint32_t kSortRounds = 8;
-constexpr uint32_t kSortTile = kSortThreads * kSortRounds;
-constexpr uint32_t kWaveSpan = 64u * kSortRounds;
+constexpr uint32_t kWalkWaves = 4;  // waves (groups) per walk / pieces / carry workgroup
 
 struct RDg {  // a completing record's datagram before its place is known (16 B)
   uint32_t payload_len, nfrags;
@@ -125,8 +122,7 @@ struct IrArgs {
   uint64_t *res;
   uint32_t *tab, tmask;
   uint32_t *slot;         // M
-  uint2 *pa, *pb;         // M pairs each
-  uint32_t *hist, ntile;  // [256][ntile]
+  uint2 *pa;              // M: the (first item of the key, item) pairs the sort takes
   uint32_t *order, *skey; // M: the items sorted, their keys (first item; M: none)
   uint64_t *mask;
   uint32_t *blk, nblk;    // block sums of the scan in flight: (nblk + 1) words per array
@@ -209,128 +205,14 @@ __global__ __launch_bounds__(256) void ir_pair_kernel(IrArgs A) {
   A.pa[i] = make_uint2(h == kNone ? A.M : A.tab[h], i);
 }
 
-// ---- the radix sort of (key, item) pairs: the scheme of gpd_tcpseg.hip ---------------------------
-__device__ __forceinline__ uint64_t match_digit(bool valid, uint32_t d) {
-  uint64_t m = __ballot(valid);
-#pragma unroll
-  for (uint32_t b = 0; b < 8u; ++b) {
-    const bool bit = (d >> b) & 1u;
-    const uint64_t bal = __ballot(valid && bit);
-    m &= bit ? bal : ~bal;
+// ---- the sort of the (key, item) pairs (gpd_radix_sort.h): where its last pass puts them ----------
+struct OrderSink {
+  uint32_t *order, *skey;
+  __device__ __forceinline__ void operator()(uint32_t pos, uint2 p) const {
+    order[pos] = p.y;
+    skey[pos] = p.x;
   }
-  return m;
-}
-__device__ __forceinline__ uint32_t tile_item(uint32_t w, uint32_t lane, uint32_t r) {
-  return blockIdx.x * kSortTile + w * kWaveSpan + r * 64u + lane;
-}
-
-__global__ __launch_bounds__(kSortThreads) void is_hist_kernel(IrArgs A, const uint2 *in, uint32_t shift) {
-  __shared__ uint32_t h[256];
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  if (t < 256u) h[t] = 0;
-  __syncthreads();
-#pragma unroll
-  for (uint32_t r = 0; r < kSortRounds; ++r) {
-    const uint32_t j = tile_item(w, lane, r);
-    const bool valid = j < A.M;
-    const uint32_t d = valid ? (in[j].x >> shift) & 255u : 0u;
-    const uint64_t m = match_digit(valid, d);
-    if (valid && (m & ((1ull << lane) - 1ull)) == 0ull) atomicAdd(&h[d], (uint32_t)__popcll(m));
-  }
-  __syncthreads();
-  if (t < 256u) A.hist[t * A.ntile + blockIdx.x] = h[t];
-}
-
-// One workgroup: exclusive scan of hist[256 * ntile] in place, sixteen consecutive entries a lane
-// a round (16,384 entries between barriers).
-__global__ __launch_bounds__(1024) void is_scan_kernel(IrArgs A) {
-  __shared__ uint32_t wtot[16];
-  __shared__ uint32_t carry;
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  const uint32_t nent = 256u * A.ntile;  // a multiple of 16
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (uint32_t c0 = 0; c0 < nent; c0 += 16384u) {
-    const uint32_t k = c0 + 16u * t;
-    uint4 v[4];
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < 4u; ++q) {
-      v[q] = k < nent ? *reinterpret_cast<const uint4 *>(A.hist + k + 4u * q) : make_uint4(0u, 0u, 0u, 0u);
-      s += v[q].x + v[q].y + v[q].z + v[q].w;
-    }
-    const uint32_t x = wave_scan32(s, lane);
-    if (lane == 63u) wtot[w] = x;
-    __syncthreads();
-    uint32_t before = carry;
-    for (uint32_t j = 0; j < w; ++j) before += wtot[j];
-    uint32_t e = before + x - s;
-    if (k < nent) {
-#pragma unroll
-      for (uint32_t q = 0; q < 4u; ++q) {
-        *reinterpret_cast<uint4 *>(A.hist + k + 4u * q) = make_uint4(e, e + v[q].x, e + v[q].x + v[q].y,
-                                                                     e + v[q].x + v[q].y + v[q].z);
-        e += v[q].x + v[q].y + v[q].z + v[q].w;
-      }
-    }
-    __syncthreads();
-    if (t == 1023u) carry = before + x;
-    __syncthreads();
-  }
-}
-
-// Stable scatter of one tile (see gpd_tcpseg.hip sort_scatter_kernel).  LAST: the item and its
-// key go to their final arrays.
-template <bool LAST>
-__global__ __launch_bounds__(kSortThreads) void is_scatter_kernel(IrArgs A, const uint2 *in, uint2 *out,
-                                                                    uint32_t shift) {
-  __shared__ uint32_t base[kSortWaves][256];
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  for (uint32_t k = t; k < kSortWaves * 256u; k += kSortThreads) (&base[0][0])[k] = 0;
-  __syncthreads();
-  uint2 p[kSortRounds];
-  uint32_t below[kSortRounds], tot[kSortRounds];
-#pragma unroll
-  for (uint32_t r = 0; r < kSortRounds; ++r) {
-    const uint32_t j = tile_item(w, lane, r);
-    const bool valid = j < A.M;
-    p[r] = valid ? in[j] : make_uint2(0u, 0u);
-    const uint32_t d = (p[r].x >> shift) & 255u;
-    const uint64_t m = match_digit(valid, d);
-    below[r] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    tot[r] = (valid && below[r] == 0u) ? (uint32_t)__popcll(m) : 0u;
-    if (tot[r]) base[w][d] += tot[r];
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
-  if (t < 256u) {
-    uint32_t b = A.hist[t * A.ntile + blockIdx.x];
-    for (uint32_t k = 0; k < kSortWaves; ++k) {
-      const uint32_t c = base[k][t];
-      base[k][t] = b;
-      b += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (uint32_t r = 0; r < kSortRounds; ++r) {
-    const bool valid = tile_item(w, lane, r) < A.M;
-    const uint32_t d = (p[r].x >> shift) & 255u;
-    const uint32_t b = base[w][d];
-    __builtin_amdgcn_wave_barrier();
-    if (tot[r]) base[w][d] = b + tot[r];
-    __builtin_amdgcn_wave_barrier();
-    if (valid) {
-      const uint32_t pos = b + below[r];
-      if (LAST) {
-        A.order[pos] = p[r].y;
-        A.skey[pos] = p[r].x;
-      } else {
-        out[pos] = p[r];
-      }
-    }
-  }
-}
+};
 
 // ---- groups and their private regions -----------------------------------------------------------
 __global__ __launch_bounds__(256) void ir_head_kernel(IrArgs A) {
@@ -595,103 +477,6 @@ __global__ __launch_bounds__(64 * kWalkWaves) void ir_carry_kernel(IrArgs A) {
   }
 }
 
-// ---- the gather -----------------------------------------------------------------------------------
-struct GaArgs {
-  const IprPiece *pieces;
-  uint32_t np;
-  uint8_t *out;
-  uint64_t nbytes;
-  const uint8_t *base[2];  // by IprPiece::where
-  uint64_t lim[2], len[2]; // lim: len rounded up to 16, the end of what a 16-byte load may touch
-};
-struct GRec {    // a wave's piece as the chunks see it (LDS, 24 bytes)
-  uint64_t pos;  // where its bytes start in the output
-  uint32_t src, len, where, pad;
-};
-
-// ta_gather_kernel's scheme (gpd_tcpstream.hip) with a source base per piece.  A wave per 64
-// consecutive pieces; their bytes are the contiguous run [P0, P1) of the output.  The wave owns
-// the 16-byte output chunks that start inside its run.  A chunk is assembled in registers from
-// the pieces it covers, each two aligned 16-byte source loads shifted together and masked, and
-// leaves as one 16-byte non-temporal store.  Pieces can be 0 to 15 bytes long, so the run's last
-// chunk may reach into any number of later waves' pieces: that chunk, and the output's ragged
-// end, go byte by byte.  Nothing is stored at or past nbytes.
-__global__ __launch_bounds__(64 * kGatherWaves) void ir_gather_kernel(GaArgs A) {
-  __shared__ GRec s_rec[kGatherWaves][64];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint64_t r0 = ((uint64_t)blockIdx.x * kGatherWaves + w) * 64u;
-  const bool wlive = r0 < A.np;
-  const uint64_t ri = r0 + lane;
-  GRec q{~0ull, 0u, 0u, 0u, 0u};
-  if (ri < A.np) {
-    const v4u a = *reinterpret_cast<const v4u *>(A.pieces + ri);  // src, len, pos, where
-    q.pos = a.z;
-    q.src = a.x;
-    q.len = a.y;
-    q.where = a.w & 1u;
-  }
-  s_rec[w][lane] = q;
-  __syncthreads();
-  if (!wlive) return;
-  const uint32_t nl = A.np - r0 < 64ull ? (uint32_t)(A.np - r0) : 64u;
-  const uint64_t P0 = shfl64(q.pos, 0), P1 = shfl64(q.pos + q.len, (int)nl - 1);
-  const GRec *rec = s_rec[w];
-  const uint64_t c_lo = (P0 + 15ull) >> 4, c_hi = (P1 + 15ull) >> 4;
-  const v4u z{0u, 0u, 0u, 0u};
-  const uint8_t *base0 = A.base[0], *base1 = A.base[1];
-  const uint64_t lim0 = A.lim[0], lim1 = A.lim[1];
-  for (uint64_t c = c_lo + lane; c < c_hi; c += 64ull) {
-    const uint64_t cb = c << 4, ce = cb + 16ull;
-    if (ce > P1 && P1 < A.nbytes) {  // reaches into later waves' pieces: byte by byte
-      const uint64_t end = ce < A.nbytes ? ce : A.nbytes;
-      uint32_t lo = 0;
-#pragma unroll
-      for (uint32_t step = 32; step >= 1u; step >>= 1)
-        if (rec[lo + step].pos <= cb) lo += step;
-      uint64_t k = r0 + lo, x = cb;
-      while (x < end && k < A.np) {
-        const IprPiece R = A.pieces[k];
-        if (R.pos > x) break;  // (cannot happen: the pieces' bytes are back to back)
-        if ((uint64_t)R.pos + R.len <= x) {
-          ++k;
-          continue;
-        }
-        const uint64_t sa = (uint64_t)R.src + (x - R.pos);
-        A.out[x] = sa < A.len[R.where & 1u] ? A.base[R.where & 1u][sa] : (uint8_t)0;
-        ++x;
-      }
-      continue;
-    }
-    const uint64_t end = ce < P1 ? ce : P1;  // (end < ce: P1 == nbytes, the output's ragged end)
-    v4u V = z;
-    uint64_t x = cb;
-    while (x < end) {
-      uint32_t lo = 0;  // the last piece with pos <= x: the one x lies in
-#pragma unroll
-      for (uint32_t step = 32; step >= 1u; step >>= 1)
-        if (rec[lo + step].pos <= x) lo += step;
-      const GRec t = rec[lo];
-      const uint64_t qe = t.pos + t.len;
-      if (qe <= x) break;  // (cannot happen: x < P1)
-      const uint64_t pe = qe < end ? qe : end;
-      const int32_t k0 = (int32_t)(x - cb), k1 = (int32_t)(pe - cb);
-      // (the two bases stay in scalar registers: indexing A.base by lane would be a load per chunk)
-      V |= src16_of(t.where ? base1 : base0, t.where ? lim1 : lim0, (int64_t)t.src + (int64_t)(x - t.pos) - k0) &
-           byte_mask(k0, k1);
-      x = pe;
-    }
-    if (end == ce) {
-      __builtin_nontemporal_store(V, reinterpret_cast<v4u *>(A.out + cb));
-    } else {
-      const uint32_t wds[4] = {V.x, V.y, V.z, V.w};
-      const uint32_t vend = (uint32_t)(end - cb);
-#pragma unroll
-      for (uint32_t b = 0; b < 16u; ++b)
-        if (b < vend) A.out[cb + b] = (uint8_t)(wds[b >> 2] >> ((b & 3u) * 8u));
-    }
-  }
-}
-
 // One lane per datagram: the three header patches of include/gpd_ip4reasm.h.
 __global__ __launch_bounds__(256) void ir_patch_kernel(IrArgs A, uint64_t nbytes) {
   const uint32_t k = blockIdx.x * 256u + threadIdx.x;
@@ -726,46 +511,6 @@ __global__ __launch_bounds__(256) void ir_discard_kernel(IprListRec *lists, uint
   atomicAdd(reinterpret_cast<unsigned long long *>(res), 1ull);
   atomicAdd(reinterpret_cast<unsigned long long *>(res + 1), (unsigned long long)R.nn);
   atomicAdd(reinterpret_cast<unsigned long long *>(res + 2), (unsigned long long)R.nbytes);
-}
-
-#define IR_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-  } while (0)
-
-inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-
-// Device memory of at least `bytes` at *p (grown by replacement: the old contents are not kept).
-template <class T>
-bool grow(T **p, size_t *cap, size_t bytes) {
-  if (*cap >= bytes && *p) return true;
-  const size_t want = std::max(bytes + bytes / 2, (size_t)4096);
-  void *q = nullptr;
-  if (hipMalloc(&q, want) != hipSuccess) return false;
-  if (*p) (void)hipFree(*p);
-  *p = static_cast<T *>(q);
-  *cap = want;
-  return true;
-}
-
-void gather(const IrArgs &A, const IprPiece *pieces, uint32_t np, uint8_t *out, uint64_t nbytes, const uint8_t *store,
-            uint64_t store_len, hipStream_t s) {
-  if (!np || !nbytes) return;
-  GaArgs G{};
-  G.pieces = pieces;
-  G.np = np;
-  G.out = out;
-  G.nbytes = nbytes;
-  G.base[kIprStore] = store;
-  G.len[kIprStore] = store_len;
-  G.lim[kIprStore] = (store_len + 15ull) & ~15ull;
-  G.base[kIprBatch] = A.data;
-  G.len[kIprBatch] = A.dlen;
-  G.lim[kIprBatch] = (A.dlen + 15ull) & ~15ull;
-  const uint32_t nwave = (np + 63u) / 64u;
-  hipLaunchKernelGGL(ir_gather_kernel, dim3((nwave + kGatherWaves - 1u) / kGatherWaves), dim3(64 * kGatherWaves), 0, s, G);
 }
 
 }  // namespace
@@ -813,14 +558,14 @@ extern "C" int gpd_ip4_defrag_discard(gpd_ip4_defrag *d, uint64_t t_ns, uint64_t
   IprCarry &C = d->c[d->cur];
   if (C.nl == 0) return GPD_OK;
   DeviceScope dscope_;
-  IR_TRY(dscope_.set(d->device));
+  GPD_TRY(dscope_.set(d->device));
   if (!grow(&d->scratch, &d->scratch_bytes, 64)) return set_error(GPD_ERR_NOMEM, "%s: scratch allocation failed", who);
   uint64_t *res = reinterpret_cast<uint64_t *>(d->scratch);
-  IR_TRY(hipMemsetAsync(res, 0, 64, nullptr));
+  GPD_TRY(hipMemsetAsync(res, 0, 64, nullptr));
   hipLaunchKernelGGL(ir_discard_kernel, dim3((C.nl + 255u) / 256u), dim3(256), 0, nullptr, C.lists, C.nl, t_ns, res);
-  IR_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint64_t got[3] = {0, 0, 0};
-  IR_TRY(hipMemcpy(got, res, 24, hipMemcpyDeviceToHost));
+  GPD_TRY(hipMemcpy(got, res, 24, hipMemcpyDeviceToHost));
   for (int k = 0; k < 3; ++k) d->live[k] -= std::min(got[k], d->live[k]);
   *n = got[0];
   return GPD_OK;
@@ -861,7 +606,7 @@ extern "C" int gpd_ip4_defrag_run(gpd_ip4_defrag *d, const gpd_batch *in, const 
     return set_error(GPD_ERR_INVALID, "%s: data_len %llu outside the 32-bit offset range", who,
                      (unsigned long long)in->data_len);
   DeviceScope dscope_;
-  IR_TRY(dscope_.set(d->device));
+  GPD_TRY(dscope_.set(d->device));
   const hipStream_t s = (hipStream_t)stream;
   IprCarry &New = d->c[d->cur ^ 1];
   IrArgs A{};
@@ -887,7 +632,7 @@ extern "C" int gpd_ip4_defrag_run(gpd_ip4_defrag *d, const gpd_batch *in, const 
   uint32_t tcap = 64;
   while (tcap < 2ull * M) tcap <<= 1;
   A.tmask = tcap - 1u;
-  A.ntile = (M + kSortTile - 1u) / kSortTile;
+  const uint32_t ntile = (M + kSortTile - 1u) / kSortTile;
   const uint32_t nblk_m = (M + kCompactBlock - 1u) / kCompactBlock, nblk_r = (cnt + kCompactBlock - 1u) / kCompactBlock;
   // the scratch, carved in one piece
   size_t at = 0;
@@ -897,7 +642,7 @@ extern "C" int gpd_ip4_defrag_run(gpd_ip4_defrag *d, const gpd_batch *in, const 
     return a;
   };
   const size_t o_res = take(kResWords * 8), o_tab = take((size_t)tcap * 4), o_slot = take((size_t)M * 4);
-  const size_t o_pa = take((size_t)M * 8), o_pb = take((size_t)M * 8), o_hist = take((size_t)A.ntile * 256 * 4);
+  const size_t o_pa = take((size_t)M * 8), o_pb = take((size_t)M * 8), o_hist = take((size_t)ntile * 256 * 4);
   const size_t o_order = take((size_t)M * 4), o_skey = take((size_t)M * 4), o_mask = take(((size_t)M + 63) / 64 * 8);
   const size_t o_blk = take(3 * ((size_t)nblk_m + 1) * 4), o_heads = take((size_t)M * 4);
   const size_t o_wbase = take(((size_t)M + 1) * 4), o_pnodes = take(W * sizeof(IprNode));
@@ -911,8 +656,8 @@ extern "C" int gpd_ip4_defrag_run(gpd_ip4_defrag *d, const gpd_batch *in, const 
   A.tab = reinterpret_cast<uint32_t *>(sb + o_tab);
   A.slot = reinterpret_cast<uint32_t *>(sb + o_slot);
   A.pa = reinterpret_cast<uint2 *>(sb + o_pa);
-  A.pb = reinterpret_cast<uint2 *>(sb + o_pb);
-  A.hist = reinterpret_cast<uint32_t *>(sb + o_hist);
+  uint2 *pb = reinterpret_cast<uint2 *>(sb + o_pb);
+  const SortArgs S{M, ntile, reinterpret_cast<uint32_t *>(sb + o_hist)};
   A.order = reinterpret_cast<uint32_t *>(sb + o_order);
   A.skey = reinterpret_cast<uint32_t *>(sb + o_skey);
   A.mask = reinterpret_cast<uint64_t *>(sb + o_mask);
@@ -931,35 +676,24 @@ extern "C" int gpd_ip4_defrag_run(gpd_ip4_defrag *d, const gpd_batch *in, const 
   A.cpieces = reinterpret_cast<IprPiece *>(sb + o_cpieces);
 
   // group: keys, first items, the sort, the heads
-  IR_TRY(hipMemsetAsync(A.res, 0, kResWords * 8, s));
-  IR_TRY(hipMemsetAsync(A.tab, 0xFF, (size_t)tcap * 4, s));
-  IR_TRY(hipMemsetAsync(A.rsc, 0, 3 * (size_t)cnt * 4, s));
+  GPD_TRY(hipMemsetAsync(A.res, 0, kResWords * 8, s));
+  GPD_TRY(hipMemsetAsync(A.tab, 0xFF, (size_t)tcap * 4, s));
+  GPD_TRY(hipMemsetAsync(A.rsc, 0, 3 * (size_t)cnt * 4, s));
   const unsigned igrid = (M + 255u) / 256u;
   hipLaunchKernelGGL(ir_key_kernel, dim3(igrid), dim3(256), 0, s, A);
   hipLaunchKernelGGL(ir_pair_kernel, dim3(igrid), dim3(256), 0, s, A);
-  uint32_t bits = 0;
-  for (uint32_t v = M; v; v >>= 1) ++bits;
-  const uint32_t passes = std::max(1u, (bits + 7u) / 8u);
-  uint2 *src = A.pa, *dst = A.pb;
-  for (uint32_t p = 0; p < passes; ++p) {
-    hipLaunchKernelGGL(is_hist_kernel, dim3(A.ntile), dim3(kSortThreads), 0, s, A, src, 8u * p);
-    hipLaunchKernelGGL(is_scan_kernel, dim3(1), dim3(1024), 0, s, A);
-    if (p + 1 == passes)
-      hipLaunchKernelGGL(is_scatter_kernel<true>, dim3(A.ntile), dim3(kSortThreads), 0, s, A, src, dst, 8u * p);
-    else
-      hipLaunchKernelGGL(is_scatter_kernel<false>, dim3(A.ntile), dim3(kSortThreads), 0, s, A, src, dst, 8u * p);
-    std::swap(src, dst);
-  }
+  const uint32_t passes = sort_passes(M);  // keys lie in [0, M]; M: no key
+  sort_last_pass(S, sort_leading_passes(S, A.pa, pb, passes, s), passes, OrderSink{A.order, A.skey}, s);
   A.nblk = nblk_m;
   hipLaunchKernelGGL(ir_head_kernel, dim3(nblk_m), dim3(256), 0, s, A);
   hipLaunchKernelGGL(ir_scan_kernel, dim3(1), dim3(1024), 0, s, A);
   hipLaunchKernelGGL(ir_index_kernel, dim3(nblk_m), dim3(64), 0, s, A);
-  IR_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint32_t ng = 0;
   uint64_t bad = 0;
-  IR_TRY(hipMemcpyAsync(&ng, A.blk + nblk_m, 4, hipMemcpyDeviceToHost, s));
-  IR_TRY(hipMemcpyAsync(&bad, A.res + kResBad, 8, hipMemcpyDeviceToHost, s));
-  IR_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(&ng, A.blk + nblk_m, 4, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipMemcpyAsync(&bad, A.res + kResBad, 8, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   if (bad)
     return set_error(GPD_ERR_INVALID, "%s: frags[] is not a complete hand-off of this batch (packets out of order "
                      "or outside it)", who);
@@ -981,10 +715,10 @@ extern "C" int gpd_ip4_defrag_run(gpd_ip4_defrag *d, const gpd_batch *in, const 
   hipLaunchKernelGGL(ir_scan_kernel, dim3(3), dim3(1024), 0, s, A);
   hipLaunchKernelGGL(ir_gapply_kernel, dim3(nblk_g, 3), dim3(256), 0, s, A);
   hipLaunchKernelGGL(ir_gtotals_kernel, dim3(1), dim3(64), 0, s, A);
-  IR_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint64_t tot[kResWords] = {};
-  IR_TRY(hipMemcpyAsync(tot, A.res, sizeof tot, hipMemcpyDeviceToHost, s));
-  IR_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(tot, A.res, sizeof tot, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   out[0] = tot[kResDgrams];
   out[2] = tot[kResBytes];
   out[3] = tot[kResLists];
@@ -1015,13 +749,18 @@ extern "C" int gpd_ip4_defrag_run(gpd_ip4_defrag *d, const gpd_batch *in, const 
   hipLaunchKernelGGL(ir_place_kernel, dim3((cnt + 255u) / 256u), dim3(256), 0, s, A);
   if (A.ndg) hipLaunchKernelGGL(ir_pieces_kernel, dim3((A.ndg + kWalkWaves - 1u) / kWalkWaves), dim3(64 * kWalkWaves), 0, s, A);
   if (nl2) hipLaunchKernelGGL(ir_carry_kernel, dim3(wgrid), dim3(64 * kWalkWaves), 0, s, A);
-  gather(A, A.cpieces, nf2, New.store, nb2, Old.store, Old.nb, s);
+  PieceSource G{};  // both gathers read the old store and the batch
+  G.set(kIprStore, Old.store, Old.nb);
+  G.set(kIprBatch, A.data, A.dlen);
+  G.pieces = A.cpieces;
+  launch_gather(G, nf2, New.store, nb2, s);
   if (want_bytes && A.ndg) {
-    gather(A, A.dpieces, (uint32_t)tot[kResPieces], bytes, tot[kResBytes], Old.store, Old.nb, s);
+    G.pieces = A.dpieces;
+    launch_gather(G, (uint32_t)tot[kResPieces], bytes, tot[kResBytes], s);
     hipLaunchKernelGGL(ir_patch_kernel, dim3((A.ndg + 255u) / 256u), dim3(256), 0, s, A, tot[kResBytes]);
   }
-  IR_TRY(hipGetLastError());
-  IR_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipGetLastError());
+  GPD_TRY(hipStreamSynchronize(s));
   New.nl = nl2;
   New.nf = nf2;
   New.nb = nb2;

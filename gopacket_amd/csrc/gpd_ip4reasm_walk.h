@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "../../include/gpd_ip4reasm.h"
+#include "gpd_gather.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define GPD_IPR_HD __host__ __device__ inline
@@ -31,11 +32,9 @@ struct IprNode {
 };
 constexpr uint32_t kIprStore = 0, kIprBatch = 1;
 
-// One slice build appends (16 B): bytes [src, src + len) of base `where` to the datagram's
-// payload at `pos`.
-struct IprPiece {
-  uint32_t src, len, pos, where;
-};
+// One slice build appends: bytes [src, src + len) of base `where` to the datagram's payload at
+// `pos` (the shared gather's piece, gpd_gather.h).
+using IprPiece = GatherPiece;
 
 // One key's fragmentList (:204-210); the nodes are the caller's array.
 struct IprList {

@@ -402,13 +402,6 @@ __global__ __launch_bounds__(64 * kCopyWaves) void ngw_copy_kernel(NgwArgs A) {
   }
 }
 
-#define NGW_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-  } while (0)
-
 // The context's scratch carved into A's arrays and the prefix's staging copy; the scan when
 // there are packets; res[5] back on the host.  Synchronises `s`, after which `prefix` is free.
 int scan(gpd_ctx *ctx, const char *who, NgwArgs &A, const uint8_t *prefix, bool stage, uint8_t **staged,
@@ -427,17 +420,17 @@ int scan(gpd_ctx *ctx, const char *who, NgwArgs &A, const uint8_t *prefix, bool 
   A.bnext = A.bfirst + A.nblk;
   A.wfirst = A.bnext + A.nblk;
   *staged = base + 64 + arrays;
-  if (stage && A.base0) NGW_TRY(hipMemcpyAsync(*staged, prefix, A.base0, hipMemcpyHostToDevice, s));
+  if (stage && A.base0) GPD_TRY(hipMemcpyAsync(*staged, prefix, A.base0, hipMemcpyHostToDevice, s));
   if (A.n) {
-    NGW_TRY(hipMemsetAsync(base, 0xFF, 64, s));
+    GPD_TRY(hipMemsetAsync(base, 0xFF, 64, s));
     if (A.wirelen || A.ifindex || A.n_ifaces == 0)
       hipLaunchKernelGGL(ngw_bad_kernel, dim3((A.n + 255u) / 256u), dim3(256), 0, s, A);
     hipLaunchKernelGGL(ngw_sum_kernel, dim3(A.nblk), dim3(1024), 0, s, A);
     hipLaunchKernelGGL(ngw_scan_kernel, dim3(1), dim3(1024), 0, s, A);
-    NGW_TRY(hipGetLastError());
-    NGW_TRY(hipMemcpyAsync(res, A.res, 40, hipMemcpyDeviceToHost, s));
+    GPD_TRY(hipGetLastError());
+    GPD_TRY(hipMemcpyAsync(res, A.res, 40, hipMemcpyDeviceToHost, s));
   }
-  if (A.n || (stage && A.base0)) NGW_TRY(hipStreamSynchronize(s));
+  if (A.n || (stage && A.base0)) GPD_TRY(hipStreamSynchronize(s));
   return GPD_OK;
 }
 
@@ -659,7 +652,7 @@ int gpd_pcapng_write(gpd_ctx *ctx, const gpd_batch *in, const uint64_t *ts_ns, c
   if ((!out && out_cap) || ((uintptr_t)out & 15u))
     return set_error(GPD_ERR_INVALID, "%s: out must be a 16-byte aligned buffer of out_cap bytes", who);
   DeviceScope dscope_;
-  NGW_TRY(dscope_.set(ctx_device(ctx)));
+  GPD_TRY(dscope_.set(ctx_device(ctx)));
   const hipStream_t s = (hipStream_t)stream;
   NgwArgs A{};
   A.data = in->data;
@@ -689,11 +682,11 @@ int gpd_pcapng_write(gpd_ctx *ctx, const gpd_batch *in, const uint64_t *ts_ns, c
     if (res[0] > out_cap)
       return set_error(GPD_ERR_INVALID, "%s: the stream takes %llu bytes (%llu records), out_cap is %llu", who,
                        (unsigned long long)res[0], (unsigned long long)res[1], (unsigned long long)out_cap);
-    if (A.base0) NGW_TRY(hipMemcpyAsync(out, staged, A.base0, hipMemcpyDeviceToDevice, s));
+    if (A.base0) GPD_TRY(hipMemcpyAsync(out, staged, A.base0, hipMemcpyDeviceToDevice, s));
     if (res[1]) {
       hipLaunchKernelGGL(ngw_copy_kernel, dim3((A.nwave + kCopyWaves - 1u) / kCopyWaves), dim3(64 * kCopyWaves),
                          0, s, A);
-      NGW_TRY(hipGetLastError());
+      GPD_TRY(hipGetLastError());
     }
   }
   if (res[2] != ~0ull) {

@@ -413,13 +413,6 @@ __global__ __launch_bounds__(64) void pw_head_kernel(WrArgs A) {
   if (t < kFileHeader) A.out[t] = (uint8_t)(A.fh[t >> 2] >> ((t & 3u) * 8u));
 }
 
-#define PW_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-  } while (0)
-
 void file_header_words(uint32_t flags, uint32_t snaplen, uint32_t linktype, uint32_t w[6]) {
   w[0] = (flags & GPD_PCAPW_NANOS) ? 0xA1B23C4Du : 0xA1B2C3D4u;  // write.go:82-86
   w[1] = 2u | (4u << 16);                                        // versionMajor, versionMinor
@@ -445,13 +438,13 @@ int scan(gpd_ctx *ctx, const char *who, WrArgs &A, hipStream_t s, uint64_t res[4
   A.bnext = A.bfirst + A.nblk;
   A.wcnt = A.bnext + A.nblk;
   A.wfirst = A.wcnt + A.nwave;
-  PW_TRY(hipMemsetAsync(base, 0xFF, 64, s));
+  GPD_TRY(hipMemsetAsync(base, 0xFF, 64, s));
   if (PCAP && A.wirelen) hipLaunchKernelGGL(pw_bad_kernel, dim3((A.n + 255u) / 256u), dim3(256), 0, s, A);
   hipLaunchKernelGGL(pw_sum_kernel<PCAP>, dim3(A.nblk), dim3(1024), 0, s, A);
   hipLaunchKernelGGL(pw_scan_kernel, dim3(1), dim3(1024), 0, s, A);
-  PW_TRY(hipGetLastError());
-  PW_TRY(hipMemcpyAsync(res, A.res, 32, hipMemcpyDeviceToHost, s));
-  PW_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipGetLastError());
+  GPD_TRY(hipMemcpyAsync(res, A.res, 32, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   return GPD_OK;
 }
 
@@ -511,7 +504,7 @@ int gpd_pcap_write(gpd_ctx *ctx, const gpd_batch *in, const uint64_t *ts_ns, con
   if ((!out && out_cap) || ((uintptr_t)out & 15u))
     return set_error(GPD_ERR_INVALID, "%s: out must be a 16-byte aligned buffer of out_cap bytes", who);
   DeviceScope dscope_;
-  PW_TRY(dscope_.set(ctx_device(ctx)));
+  GPD_TRY(dscope_.set(ctx_device(ctx)));
   const hipStream_t s = (hipStream_t)stream;
   WrArgs A{};
   fill_in(A, in, keep);
@@ -536,10 +529,10 @@ int gpd_pcap_write(gpd_ctx *ctx, const gpd_batch *in, const uint64_t *ts_ns, con
     if (res[1]) {
       hipLaunchKernelGGL(pw_copy_kernel<true>, dim3((A.nwave + kCopyWaves - 1u) / kCopyWaves),
                          dim3(64 * kCopyWaves), 0, s, A);
-      PW_TRY(hipGetLastError());
+      GPD_TRY(hipGetLastError());
     } else if (A.base0) {
       hipLaunchKernelGGL(pw_head_kernel, dim3(1), dim3(64), 0, s, A);
-      PW_TRY(hipGetLastError());
+      GPD_TRY(hipGetLastError());
     }
   }
   if (res[2] != ~0ull)
@@ -563,7 +556,7 @@ int gpd_batch_select(gpd_ctx *ctx, const gpd_batch *in, const uint8_t *keep,
     return set_error(GPD_ERR_INVALID, "%s: out_data must be a 16-byte aligned buffer of out_cap bytes", who);
   if (in->n == 0) return GPD_OK;
   DeviceScope dscope_;
-  PW_TRY(dscope_.set(ctx_device(ctx)));
+  GPD_TRY(dscope_.set(ctx_device(ctx)));
   const hipStream_t s = (hipStream_t)stream;
   WrArgs A{};
   fill_in(A, in, keep);
@@ -588,7 +581,7 @@ int gpd_batch_select(gpd_ctx *ctx, const gpd_batch *in, const uint8_t *keep,
   if (!out_offset || !out_caplen) return set_error(GPD_ERR_INVALID, "%s: null out_offset / out_caplen", who);
   hipLaunchKernelGGL(pw_copy_kernel<false>, dim3((A.nwave + kCopyWaves - 1u) / kCopyWaves), dim3(64 * kCopyWaves),
                      0, s, A);
-  PW_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   return GPD_OK;
 }
 

@@ -1,15 +1,16 @@
-// gpd_radix_sort.h — the device sort the hand-off (gpd_tcpseg.hip) and the connection tracker
-// (gpd_tcptrack.hip) share, one copy for both: a stable LSD radix sort of (key, index) pairs, 8
-// bits a pass.  Each pass is three launches and no kernel waits on another workgroup (no
-// decoupled look-back, no spin on a global word): passes are separated by launch boundaries only.
+// gpd_radix_sort.h — the device sort the hand-off (gpd_tcpseg.hip), the connection tracker
+// (gpd_tcptrack.hip) and the IPv4 reassembly (gpd_ip4reasm.hip) share, one copy for the three: a
+// stable LSD radix sort of (key, index) pairs, 8 bits a pass.  Each pass is three launches and no
+// kernel waits on another workgroup: passes are separated by launch boundaries only.
 //
 //   sort_hist_kernel    per workgroup tile of kSortTile pairs: counts per digit, [digit][tile]
 //   sort_scan_kernel    one workgroup: exclusive scan of the [digit][tile] counts in place
 //   sort_scatter_kernel stable ranks inside the tile: per wave eight ballots give the lanes
 //                       with the same digit, the rank is the popcount below the lane, and the
 //                       waves' bases are scanned in wave order through LDS.  Where a pair goes is
-//                       the caller's Sink: the other pair array, or (the hand-off's last pass) the
-//                       gather of what the pair stands for.
+//                       the caller's Sink: the other pair array, or in the last pass what the user
+//                       keeps (the hand-off gathers what the pair stands for, reassembly splits
+//                       the pair into its order[] and skey[]).
 //
 // The kernels have internal linkage: every translation unit that includes this compiles its own.
 #pragma once

@@ -1,7 +1,7 @@
-// gpd_stream_util.h — device helpers the stream builders share (the TCP stream assembly,
-// gpd_tcpstream.hip, and the IPv4 reassembly, gpd_ip4reasm.hip): the two-level scan over an
-// array of per-item values (block sums, gpd_compact.h's compact_scan over them, the prefix per
-// item) and the byte shuffles of the 16-byte gather.  No kernel here waits on another workgroup.
+// gpd_stream_util.h — device helpers the stream builders share (gpd_tcpstream.hip,
+// gpd_ip4reasm.hip, gpd_tcpasm.hip): the two-level scan over an array of per-item values (block
+// sums, gpd_compact.h's compact_scan over them, the prefix per item) and the byte shuffles of the
+// 16-byte gather (gpd_gather.h).  No kernel here waits on another workgroup.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

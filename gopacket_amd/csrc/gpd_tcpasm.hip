@@ -25,14 +25,15 @@
 //   tam_place_kernel        one wave per item: records, seen_ns, stream record and the output
 //                           pieces to their dense places; the connection and its remaining pages
 //                           (list order) to the new carry, with one piece per page
-//   tam_gather_kernel (x2)  ir_gather_kernel's scheme (gpd_ip4reasm.hip): output bytes, then the
-//                           new store's bytes, each from the batch and the old store
+//   gather_kernel (x2)      the shared bandwidth path (gpd_gather.h): output bytes, then the new
+//                           store's bytes, each from the batch and the old store
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <new>
 
 #include "gpd_compact.h"
+#include "gpd_gather.h"
 #include "gpd_internal.h"
 #include "gpd_stream_util.h"
 #include "gpd_tcpasm_walk.h"
@@ -68,14 +69,9 @@ static_assert(sizeof(gpd_tcp_conn_info) == 24 && sizeof(gpd_tcp_flush) == 16 && 
                   sizeof(TamCarried) == 32 && sizeof(gpd_tcp_reasm) == 32 && sizeof(gpd_tcp_stream) == 48,
               "include/gpd_tcpasm.h layouts");
 
-constexpr uint32_t kWalkWaves = 4;    // waves (items) per walk / place workgroup
-constexpr uint32_t kGatherWaves = 4;  // waves per gather workgroup
-constexpr uint32_t kStoreSrc = 0, kBatchSrc = 1;
-
-// One slice a gather copies (16 B): bytes [src, src + len) of base `where` to the output at pos.
-struct TamPiece {
-  uint32_t src, len, pos, where;
-};
+constexpr uint32_t kWalkWaves = 4;  // waves (items) per walk / place workgroup
+constexpr uint32_t kStoreSrc = 0, kBatchSrc = 1;  // GatherPiece::where
+using TamPiece = GatherPiece;
 
 // per-item arrays that are summed and scanned
 enum { kIRec = 0, kIBytes, kIStream, kIPages, kIPageBytes, kICalls, kIAfter, kIBefore, kIWith, kItemArrays };
@@ -404,125 +400,7 @@ __global__ __launch_bounds__(64 * kWalkWaves) void tam_place_kernel(TmArgs A) {
   }
 }
 
-// ---- the gather -------------------------------------------------------------------------------------
-struct GaArgs {
-  const TamPiece *pieces;
-  uint32_t np;
-  uint8_t *out;
-  uint64_t nbytes;
-  const uint8_t *base[2];   // by TamPiece::where
-  uint64_t lim[2], len[2];  // lim: len rounded up to 16, the end of what a 16-byte load may touch
-};
-struct GRec {    // a wave's piece as the chunks see it (LDS, 24 bytes)
-  uint64_t pos;  // where its bytes start in the output
-  uint32_t src, len, where, pad;
-};
-
-// ir_gather_kernel's scheme (gpd_ip4reasm.hip).  A wave per 64 consecutive pieces; their bytes are
-// the contiguous run [P0, P1) of the output.  The wave owns the 16-byte output chunks that start
-// inside its run.  A chunk is assembled in registers from the pieces it covers, each two aligned
-// 16-byte source loads shifted together and masked, and leaves as one 16-byte non-temporal store.
-// Pieces can be 0 to 15 bytes long, so the run's last chunk may reach into any number of later
-// waves' pieces: that chunk, and the output's ragged end, go byte by byte.  Nothing is read
-// outside [0, lim) of either source, nothing is stored at or past nbytes.
-__global__ __launch_bounds__(64 * kGatherWaves) void tam_gather_kernel(GaArgs A) {
-  __shared__ GRec s_rec[kGatherWaves][64];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint64_t r0 = ((uint64_t)blockIdx.x * kGatherWaves + w) * 64u;
-  const bool wlive = r0 < A.np;
-  const uint64_t ri = r0 + lane;
-  GRec q{~0ull, 0u, 0u, 0u, 0u};
-  if (ri < A.np) {
-    const v4u a = *reinterpret_cast<const v4u *>(A.pieces + ri);  // src, len, pos, where
-    q.pos = a.z;
-    q.src = a.x;
-    q.len = a.y;
-    q.where = a.w & 1u;
-  }
-  s_rec[w][lane] = q;
-  __syncthreads();
-  if (!wlive) return;
-  const uint32_t nl = A.np - r0 < 64ull ? (uint32_t)(A.np - r0) : 64u;
-  const uint64_t P0 = shfl64(q.pos, 0), P1 = shfl64(q.pos + q.len, (int)nl - 1);
-  const GRec *rec = s_rec[w];
-  const uint64_t c_lo = (P0 + 15ull) >> 4, c_hi = (P1 + 15ull) >> 4;
-  const v4u z{0u, 0u, 0u, 0u};
-  const uint8_t *base0 = A.base[0], *base1 = A.base[1];
-  const uint64_t lim0 = A.lim[0], lim1 = A.lim[1];
-  for (uint64_t c = c_lo + lane; c < c_hi; c += 64ull) {
-    const uint64_t cb = c << 4, ce = cb + 16ull;
-    if (ce > P1 && P1 < A.nbytes) {  // reaches into later waves' pieces: byte by byte
-      const uint64_t end = ce < A.nbytes ? ce : A.nbytes;
-      uint32_t lo = 0;
-#pragma unroll
-      for (uint32_t step = 32; step >= 1u; step >>= 1)
-        if (rec[lo + step].pos <= cb) lo += step;
-      uint64_t k = r0 + lo, x = cb;
-      while (x < end && k < A.np) {
-        const TamPiece R = A.pieces[k];
-        if (R.pos > x) break;  // (cannot happen: the pieces' bytes are back to back)
-        if ((uint64_t)R.pos + R.len <= x) {
-          ++k;
-          continue;
-        }
-        const uint64_t sa = (uint64_t)R.src + (x - R.pos);
-        A.out[x] = sa < A.len[R.where & 1u] ? A.base[R.where & 1u][sa] : (uint8_t)0;
-        ++x;
-      }
-      continue;
-    }
-    const uint64_t end = ce < P1 ? ce : P1;  // (end < ce: P1 == nbytes, the output's ragged end)
-    v4u V = z;
-    uint64_t x = cb;
-    while (x < end) {
-      uint32_t lo = 0;  // the last piece with pos <= x: the one x lies in
-#pragma unroll
-      for (uint32_t step = 32; step >= 1u; step >>= 1)
-        if (rec[lo + step].pos <= x) lo += step;
-      const GRec t = rec[lo];
-      const uint64_t qe = t.pos + t.len;
-      if (qe <= x) break;  // (cannot happen: x < P1)
-      const uint64_t pe = qe < end ? qe : end;
-      const int32_t k0 = (int32_t)(x - cb), k1 = (int32_t)(pe - cb);
-      // (the two bases stay in scalar registers: indexing A.base by lane would be a load per chunk)
-      V |= src16_of(t.where ? base1 : base0, t.where ? lim1 : lim0, (int64_t)t.src + (int64_t)(x - t.pos) - k0) &
-           byte_mask(k0, k1);
-      x = pe;
-    }
-    if (end == ce) {
-      __builtin_nontemporal_store(V, reinterpret_cast<v4u *>(A.out + cb));
-    } else {
-      const uint32_t wds[4] = {V.x, V.y, V.z, V.w};
-      const uint32_t vend = (uint32_t)(end - cb);
-#pragma unroll
-      for (uint32_t b = 0; b < 16u; ++b)
-        if (b < vend) A.out[cb + b] = (uint8_t)(wds[b >> 2] >> ((b & 3u) * 8u));
-    }
-  }
-}
-
-#define TM_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-  } while (0)
-
-inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-
-// Device memory of at least `bytes` at *p (grown by replacement: the old contents are not kept).
-template <class T>
-bool grow(T **p, size_t *cap, size_t bytes) {
-  if (*cap >= bytes && *p) return true;
-  const size_t want = std::max(bytes + bytes / 2, (size_t)4096);
-  void *q = nullptr;
-  if (hipMalloc(&q, want) != hipSuccess) return false;
-  if (*p) (void)hipFree(*p);
-  *p = static_cast<T *>(q);
-  *cap = want;
-  return true;
-}
-
+// ---- the host side ----------------------------------------------------------------------------------
 // The per-connection tables of both carries, zeroed (on the first call that needs the device).
 int ensure_tables(gpd_tcp_assembler *a, const char *who) {
   if (a->tables) return GPD_OK;
@@ -532,29 +410,11 @@ int ensure_tables(gpd_tcp_assembler *a, const char *who) {
       return set_error(GPD_ERR_NOMEM, "%s: connection table allocation failed", who);
     if (!c.node0 && hipMalloc(reinterpret_cast<void **>(&c.node0), nb * 4) != hipSuccess)
       return set_error(GPD_ERR_NOMEM, "%s: connection table allocation failed", who);
-    TM_TRY(hipMemset(c.info, 0, nb * sizeof(gpd_tcp_conn_info)));
-    TM_TRY(hipMemset(c.node0, 0, nb * 4));
+    GPD_TRY(hipMemset(c.info, 0, nb * sizeof(gpd_tcp_conn_info)));
+    GPD_TRY(hipMemset(c.node0, 0, nb * 4));
   }
   a->tables = true;
   return GPD_OK;
-}
-
-void gather(const TmArgs &A, const TamPiece *pieces, uint32_t np, uint8_t *out, uint64_t nbytes, const TamCarry &Old,
-            hipStream_t s) {
-  if (!np || !nbytes) return;
-  GaArgs G{};
-  G.pieces = pieces;
-  G.np = np;
-  G.out = out;
-  G.nbytes = nbytes;
-  G.base[kStoreSrc] = Old.store;
-  G.len[kStoreSrc] = Old.store ? Old.nbytes : 0;
-  G.lim[kStoreSrc] = (G.len[kStoreSrc] + 15ull) & ~15ull;
-  G.base[kBatchSrc] = A.data;
-  G.len[kBatchSrc] = A.data ? A.dlen : 0;
-  G.lim[kBatchSrc] = (G.len[kBatchSrc] + 15ull) & ~15ull;
-  const uint32_t nwave = (np + 63u) / 64u;
-  hipLaunchKernelGGL(tam_gather_kernel, dim3((nwave + kGatherWaves - 1u) / kGatherWaves), dim3(64 * kGatherWaves), 0, s, G);
 }
 
 }  // namespace
@@ -607,10 +467,10 @@ extern "C" int gpd_tcp_assembler_reset(gpd_tcp_assembler *a, void *stream) {
   TamCarry &C = a->c[a->cur];
   if (a->tables) {
     DeviceScope dscope_;
-    TM_TRY(dscope_.set(a->device));
+    GPD_TRY(dscope_.set(a->device));
     const hipStream_t s = (hipStream_t)stream;
-    TM_TRY(hipMemsetAsync(C.info, 0, (size_t)std::max(a->id_bound, 1u) * sizeof(gpd_tcp_conn_info), s));
-    TM_TRY(hipStreamSynchronize(s));
+    GPD_TRY(hipMemsetAsync(C.info, 0, (size_t)std::max(a->id_bound, 1u) * sizeof(gpd_tcp_conn_info), s));
+    GPD_TRY(hipStreamSynchronize(s));
   }
   C.nconn = C.nwith = C.npages = C.nbytes = 0;
   return GPD_OK;
@@ -623,14 +483,14 @@ extern "C" int gpd_tcp_assembler_conns(gpd_tcp_assembler *a, gpd_tcp_conn_info *
   if ((uintptr_t)out & 7u) return set_error(GPD_ERR_INVALID, "%s: out must be 8-byte aligned", who);
   if (a->id_bound == 0) return GPD_OK;
   DeviceScope dscope_;
-  TM_TRY(dscope_.set(a->device));
+  GPD_TRY(dscope_.set(a->device));
   const hipStream_t s = (hipStream_t)stream;
   const size_t nb = (size_t)a->id_bound * sizeof(gpd_tcp_conn_info);
   if (a->tables)
-    TM_TRY(hipMemcpyAsync(out, a->c[a->cur].info, nb, hipMemcpyDeviceToDevice, s));
+    GPD_TRY(hipMemcpyAsync(out, a->c[a->cur].info, nb, hipMemcpyDeviceToDevice, s));
   else
-    TM_TRY(hipMemsetAsync(out, 0, nb, s));
-  TM_TRY(hipStreamSynchronize(s));
+    GPD_TRY(hipMemsetAsync(out, 0, nb, s));
+  GPD_TRY(hipStreamSynchronize(s));
   return GPD_OK;
 }
 
@@ -678,7 +538,7 @@ extern "C" int gpd_tcp_assembler_run(gpd_tcp_assembler *a, const gpd_batch *in, 
   }
   if (!work && Old.nconn == 0) return GPD_OK;  // no segment and no connection: nothing to do
   DeviceScope dscope_;
-  TM_TRY(dscope_.set(a->device));
+  GPD_TRY(dscope_.set(a->device));
   if (int rc = ensure_tables(a, who)) return rc;
   const hipStream_t s = (hipStream_t)stream;
   TamCarry &New = a->c[a->cur ^ 1];
@@ -727,8 +587,8 @@ extern "C" int gpd_tcp_assembler_run(gpd_tcp_assembler *a, const gpd_batch *in, 
   A.gmark = reinterpret_cast<uint32_t *>(a->sa + o_gmark);
   A.mask = reinterpret_cast<uint64_t *>(a->sa + o_mask);
   A.xidx = reinterpret_cast<uint32_t *>(a->sa + o_xidx);
-  TM_TRY(hipMemsetAsync(A.res, 0, kResWords * 8, s));
-  TM_TRY(hipMemsetAsync(A.gmark, 0, (size_t)std::max(A.id_bound, 1u) * 4, s));
+  GPD_TRY(hipMemsetAsync(A.res, 0, kResWords * 8, s));
+  GPD_TRY(hipMemsetAsync(A.gmark, 0, (size_t)std::max(A.id_bound, 1u) * 4, s));
   if (work) {
     A.blk = blks;
     A.nblk = nblk_s;
@@ -742,13 +602,13 @@ extern "C" int gpd_tcp_assembler_run(gpd_tcp_assembler *a, const gpd_batch *in, 
     hipLaunchKernelGGL(tam_select_count_kernel, dim3(nblk_i), dim3(256), 0, s, A);
     hipLaunchKernelGGL(tam_scan_kernel, dim3(1), dim3(1024), 0, s, blkx, nblk_i);
     hipLaunchKernelGGL(tam_select_index_kernel, dim3(nblk_i), dim3(64), 0, s, A);
-    TM_TRY(hipGetLastError());
-    TM_TRY(hipMemcpyAsync(&nx, blkx + nblk_i, 4, hipMemcpyDeviceToHost, s));
+    GPD_TRY(hipGetLastError());
+    GPD_TRY(hipMemcpyAsync(&nx, blkx + nblk_i, 4, hipMemcpyDeviceToHost, s));
   }
-  TM_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint64_t first[2] = {0, 0};
-  TM_TRY(hipMemcpyAsync(first, A.res, 16, hipMemcpyDeviceToHost, s));
-  TM_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(first, A.res, 16, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   if (first[kResBad])
     return set_error(GPD_ERR_INVALID, "%s: a group's flow_id is not below id_bound %u", who, a->id_bound);
   const uint64_t npages = first[kResPages];
@@ -801,10 +661,10 @@ extern "C" int gpd_tcp_assembler_run(gpd_tcp_assembler *a, const gpd_batch *in, 
   hipLaunchKernelGGL(tam_item_sum_kernel, dim3(nblk_m, kItemArrays), dim3(256), 0, s, A);
   hipLaunchKernelGGL(tam_scan_kernel, dim3(kItemArrays), dim3(1024), 0, s, blkm, nblk_m);
   hipLaunchKernelGGL(tam_item_apply_kernel, dim3(nblk_m, kIPageBytes + 1), dim3(256), 0, s, A);
-  TM_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint64_t tot[kResWords] = {};
-  TM_TRY(hipMemcpyAsync(tot, A.res, sizeof tot, hipMemcpyDeviceToHost, s));
-  TM_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(tot, A.res, sizeof tot, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   if (tot[kResBad])
     return set_error(GPD_ERR_INVALID, "%s: groups[] overlap or repeat a flow id", who);
   const uint64_t *ti = tot + kResItem;
@@ -836,12 +696,17 @@ extern "C" int gpd_tcp_assembler_run(gpd_tcp_assembler *a, const gpd_batch *in, 
       !grow(&New.store, &New.cap_store, up16((size_t)ti[kIPageBytes]) + 16))
     return set_error(GPD_ERR_NOMEM, "%s: carry allocation failed", who);
   A.nnodes = New.nodes;
-  TM_TRY(hipMemcpyAsync(New.info, Old.info, (size_t)a->id_bound * sizeof(gpd_tcp_conn_info), hipMemcpyDeviceToDevice, s));
+  GPD_TRY(hipMemcpyAsync(New.info, Old.info, (size_t)a->id_bound * sizeof(gpd_tcp_conn_info), hipMemcpyDeviceToDevice, s));
   hipLaunchKernelGGL(tam_place_kernel, dim3(wgrid), dim3(64 * kWalkWaves), 0, s, A);
-  gather(A, A.opieces, (uint32_t)ti[kIRec], bytes, ti[kIBytes], Old, s);
-  gather(A, A.cpieces, (uint32_t)ti[kIPages], New.store, ti[kIPageBytes], Old, s);
-  TM_TRY(hipGetLastError());
-  TM_TRY(hipStreamSynchronize(s));
+  PieceSource G{};  // both gathers read the old store and the batch
+  G.set(kStoreSrc, Old.store, Old.nbytes);
+  G.set(kBatchSrc, A.data, A.dlen);
+  G.pieces = A.opieces;
+  launch_gather(G, (uint32_t)ti[kIRec], bytes, ti[kIBytes], s);
+  G.pieces = A.cpieces;
+  launch_gather(G, (uint32_t)ti[kIPages], New.store, ti[kIPageBytes], s);
+  GPD_TRY(hipGetLastError());
+  GPD_TRY(hipStreamSynchronize(s));
   New.nconn = nconn;
   New.nwith = ti[kIWith];
   New.npages = ti[kIPages];

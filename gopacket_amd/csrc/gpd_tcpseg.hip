@@ -237,15 +237,6 @@ __global__ __launch_bounds__(256) void ts_group_kernel(TsArgs A) {
   }
 }
 
-#define TS_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-  } while (0)
-
-inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-
 }  // namespace
 }  // namespace gpd
 
@@ -273,7 +264,7 @@ extern "C" int gpd_tcp_segments(gpd_ctx *ctx, const gpd_batch *in, const gpd_res
   if (!res->hdr_off || (!res->records && (!res->status || !res->layers)))
     return set_error(GPD_ERR_INVALID, "%s: needs hdr_off and status + layers (or records)", who);
   DeviceScope dscope_;
-  TS_TRY(dscope_.set(ctx_device(ctx)));
+  GPD_TRY(dscope_.set(ctx_device(ctx)));
   const hipStream_t s = (hipStream_t)stream;
   TsArgs A{};
   KParams &P = A.P;
@@ -305,10 +296,10 @@ extern "C" int gpd_tcp_segments(gpd_ctx *ctx, const gpd_batch *in, const gpd_res
   if (P.use_pages) hipLaunchKernelGGL(ts_count_kernel<true>, dim3(A.nblk), dim3(256), lds, s, A);
   else hipLaunchKernelGGL(ts_count_kernel<false>, dim3(A.nblk), dim3(256), lds, s, A);
   hipLaunchKernelGGL(ts_scan_kernel, dim3(1), dim3(1024), 0, s, A);
-  TS_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint32_t total = 0;
-  TS_TRY(hipMemcpyAsync(&total, A.blk + A.nblk, 4, hipMemcpyDeviceToHost, s));
-  TS_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(&total, A.blk + A.nblk, 4, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   *count = total;
   if (!segs && !max_out) return GPD_OK;  // the sizing call
   if (total > max_out)
@@ -331,9 +322,9 @@ extern "C" int gpd_tcp_segments(gpd_ctx *ctx, const gpd_batch *in, const gpd_res
   const unsigned rgrid = (unsigned)std::min<uint64_t>((uint64_t)ctx_num_cus(ctx) * 8, (total + 255u) / 256u);
   if (P.use_pages) hipLaunchKernelGGL(ts_record_kernel<true>, dim3(rgrid), dim3(256), lds, s, A);
   else hipLaunchKernelGGL(ts_record_kernel<false>, dim3(rgrid), dim3(256), lds, s, A);
-  TS_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   if (!flow_id) {
-    TS_TRY(hipStreamSynchronize(s));
+    GPD_TRY(hipStreamSynchronize(s));
     return GPD_OK;
   }
   const SortArgs S{total, A.ntile, A.hist};
@@ -342,15 +333,15 @@ extern "C" int gpd_tcp_segments(gpd_ctx *ctx, const gpd_batch *in, const gpd_res
   sort_last_pass(S, src, passes, SegSink{A.tmp, A.segs, A.skey}, s);
   // the groups: the compaction again, over the sorted keys' head flags
   A.nblk = (total + kCountBlock - 1u) / kCountBlock;
-  TS_TRY(hipMemsetAsync(A.res, 0, 16, s));
+  GPD_TRY(hipMemsetAsync(A.res, 0, 16, s));
   hipLaunchKernelGGL(ts_head_kernel, dim3(A.nblk), dim3(256), 0, s, A);
   hipLaunchKernelGGL(ts_scan_kernel, dim3(1), dim3(1024), 0, s, A);
   hipLaunchKernelGGL(ts_index_kernel, dim3(A.nblk), dim3(64), 0, s, A, total);
   hipLaunchKernelGGL(ts_group_kernel, dim3((total + 255u) / 256u), dim3(256), 0, s, A);
-  TS_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint64_t out[2] = {0, 0};
-  TS_TRY(hipMemcpyAsync(out, A.res, 16, hipMemcpyDeviceToHost, s));
-  TS_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(out, A.res, 16, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   *ngroups = out[0];
   *ungrouped = out[1];
   return GPD_OK;

@@ -21,13 +21,15 @@
 //   ta_totals_kernel      out[] for the host, which decides here whether anything is written
 //   ta_place_kernel       one wave per group: its records to their dense places with the final
 //                         stream_off, its stream record, its connection state
-//   ta_gather_kernel      the bandwidth path: a wave per 64 consecutive records, whose bytes are
-//                         one contiguous run of the output, in 16-byte-aligned output chunks
+//   gather_kernel         the shared bandwidth path (gpd_gather.h) with one source: a wave per 64
+//                         consecutive records, whose bytes are one contiguous run of the output,
+//                         in 16-byte-aligned output chunks
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "gpd_compact.h"
+#include "gpd_gather.h"
 #include "gpd_internal.h"
 #include "gpd_stream_util.h"
 #include "gpd_tcpstream_walk.h"
@@ -39,14 +41,9 @@ static_assert(sizeof(gpd_tcp_conn) == 8 && sizeof(gpd_tcp_asm_opts) == 8 && size
                   sizeof(gpd_tcp_stream) == 48 && sizeof(TsmNode) == 32,
               "include/gpd_tcpstream.h layouts");
 
-constexpr uint32_t kWalkWaves = 4;    // waves (groups) per walk / place workgroup
-constexpr uint32_t kGatherWaves = 4;  // waves per gather workgroup
+constexpr uint32_t kWalkWaves = 4;  // waves (groups) per walk / place workgroup
 
 struct TaArgs {
-  const uint8_t *data;
-  uint64_t dlen, lim;  // lim: data_len rounded up to 16, the end of what a 16-byte load may touch
-  const uint32_t *offset;
-  uint32_t n;
   const gpd_tcp_seg *segs;
   uint32_t cnt;
   const gpd_tcp_group *groups;
@@ -56,9 +53,6 @@ struct TaArgs {
   uint32_t max_pages, close_all;
   gpd_tcp_reasm *recs;  // the caller's
   gpd_tcp_stream *streams;
-  uint8_t *bytes;
-  uint32_t nrecs;       // known on the host after the totals
-  uint64_t nbytes;
   // scratch of the context
   uint64_t *res;        // [0..3] out[], [4] pages in all (the one atomic: a word per 2,048 segments)
   uint32_t *pbase;      // cnt + 1: a segment's first page id
@@ -243,103 +237,18 @@ __global__ __launch_bounds__(64 * kWalkWaves) void ta_place_kernel(TaArgs A) {
   }
 }
 
-// ---- the gather, 16 bytes at a time (byte shuffles: gpd_stream_util.h) ---------------------------
-__device__ inline v4u src16(const TaArgs &A, int64_t a) { return src16_of(A.data, A.lim, a); }
-
-struct GRec {    // a wave's record as the chunks see it (LDS, 24 bytes)
-  uint64_t pos;  // where its bytes start in the output
-  int64_t src;   // where they start in the batch's data
-  uint32_t len, pad;
-};
-constexpr int64_t kNoSrc = (int64_t)1 << 62;  // a record whose packet is not the batch's: zeros
-
-// A wave per 64 consecutive records; their bytes are the contiguous run [P0, P1) of the output.
-// The wave owns the 16-byte output chunks that start inside its run.  A chunk is assembled in
-// registers from the records it covers — one record for all but the chunks at record borders —
-// each piece two aligned 16-byte source loads shifted together and masked, and leaves as one
-// 16-byte store.  Records can be 0 to 15 bytes long, so the run's last chunk may reach into any
-// number of later waves' records: that chunk, and the stream's ragged end, go byte by byte.
-__global__ __launch_bounds__(64 * kGatherWaves) void ta_gather_kernel(TaArgs A) {
-  __shared__ GRec s_rec[kGatherWaves][64];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint64_t r0 = ((uint64_t)blockIdx.x * kGatherWaves + w) * 64u;
-  const bool wlive = r0 < A.nrecs;
-  const uint64_t ri = r0 + lane;
-  const bool live = ri < A.nrecs;
-  GRec q{~0ull, kNoSrc, 0u, 0u};
-  if (live) {
-    const v4u *p = reinterpret_cast<const v4u *>(A.recs + ri);
+// ---- the gather (gpd_gather.h): one source, the records loaded from recs[] ------------------------
+struct RecSource : GatherBases<1> {
+  const gpd_tcp_reasm *recs;
+  const uint32_t *offset;
+  uint32_t n;
+  __device__ __forceinline__ GatherRec load(uint64_t i) const {
+    const v4u *p = reinterpret_cast<const v4u *>(recs + i);
     const v4u a = p[0], b = p[1];  // packet, src_off, len, skip | stream_off, call, flags
-    q.pos = ((uint64_t)b.y << 32) | b.x;
-    q.len = a.z;
-    if (a.x < A.n) q.src = (int64_t)A.offset[a.x] + (int64_t)a.y;
+    // (a record whose packet is not the batch's reads as zeros)
+    return GatherRec{((uint64_t)b.y << 32) | b.x, a.x < n ? (int64_t)offset[a.x] + (int64_t)a.y : kNoSrc, a.z, 0u};
   }
-  s_rec[w][lane] = q;
-  __syncthreads();
-  if (!wlive) return;
-  const uint32_t nl = A.nrecs - r0 < 64ull ? (uint32_t)(A.nrecs - r0) : 64u;
-  const uint64_t P0 = shfl64(q.pos, 0), P1 = shfl64(q.pos + q.len, (int)nl - 1);
-  const GRec *rec = s_rec[w];
-  const uint64_t c_lo = (P0 + 15ull) >> 4, c_hi = (P1 + 15ull) >> 4;
-  const v4u z{0u, 0u, 0u, 0u};
-  for (uint64_t c = c_lo + lane; c < c_hi; c += 64ull) {
-    const uint64_t cb = c << 4, ce = cb + 16ull;
-    if (ce > P1 && P1 < A.nbytes) {  // reaches into later waves' records: byte by byte
-      const uint64_t end = ce < A.nbytes ? ce : A.nbytes;
-      uint32_t lo = 0;
-#pragma unroll
-      for (uint32_t step = 32; step >= 1u; step >>= 1)
-        if (rec[lo + step].pos <= cb) lo += step;
-      uint64_t k = r0 + lo, x = cb;
-      while (x < end && k < A.nrecs) {
-        const gpd_tcp_reasm R = A.recs[k];
-        if (R.stream_off > x) break;  // (cannot happen: the records' bytes are back to back)
-        if (R.stream_off + R.len <= x) {
-          ++k;
-          continue;
-        }
-        const uint64_t sa = R.packet < A.n ? (uint64_t)A.offset[R.packet] + R.src_off + (x - R.stream_off) : ~0ull;
-        A.bytes[x] = sa < A.dlen ? A.data[sa] : (uint8_t)0;
-        ++x;
-      }
-      continue;
-    }
-    const uint64_t end = ce < P1 ? ce : P1;  // (end < ce: P1 == nbytes, the stream's ragged end)
-    v4u V = z;
-    uint64_t x = cb;
-    while (x < end) {
-      uint32_t lo = 0;  // the last record with pos <= x: the one x lies in
-#pragma unroll
-      for (uint32_t step = 32; step >= 1u; step >>= 1)
-        if (rec[lo + step].pos <= x) lo += step;
-      const GRec t = rec[lo];
-      const uint64_t qe = t.pos + t.len;
-      if (qe <= x) break;  // (cannot happen: x < P1)
-      const uint64_t pe = qe < end ? qe : end;
-      const int32_t k0 = (int32_t)(x - cb), k1 = (int32_t)(pe - cb);
-      V |= src16(A, t.src + (int64_t)(x - t.pos) - k0) & byte_mask(k0, k1);
-      x = pe;
-    }
-    if (end == ce) {
-      __builtin_nontemporal_store(V, reinterpret_cast<v4u *>(A.bytes + cb));
-    } else {
-      const uint32_t wds[4] = {V.x, V.y, V.z, V.w};
-      const uint32_t vend = (uint32_t)(end - cb);
-#pragma unroll
-      for (uint32_t b = 0; b < 16u; ++b)
-        if (b < vend) A.bytes[cb + b] = (uint8_t)(wds[b >> 2] >> ((b & 3u) * 8u));
-    }
-  }
-}
-
-#define TA_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-  } while (0)
-
-inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+};
 
 }  // namespace
 }  // namespace gpd
@@ -376,14 +285,9 @@ extern "C" int gpd_tcp_assemble(gpd_ctx *ctx, const gpd_batch *in, const gpd_tcp
     return set_error(GPD_ERR_INVALID, "%s: data_len %llu outside the 32-bit offset range", who,
                      (unsigned long long)in->data_len);
   DeviceScope dscope_;
-  TA_TRY(dscope_.set(ctx_device(ctx)));
+  GPD_TRY(dscope_.set(ctx_device(ctx)));
   const hipStream_t s = (hipStream_t)stream;
   TaArgs A{};
-  A.data = in->data;
-  A.dlen = in->data_len;
-  A.lim = (in->data_len + 15ull) & ~15ull;
-  A.offset = in->offset;
-  A.n = (uint32_t)in->n;
   A.segs = segs;
   A.cnt = (uint32_t)count;
   A.groups = groups;
@@ -394,7 +298,6 @@ extern "C" int gpd_tcp_assemble(gpd_ctx *ctx, const gpd_batch *in, const gpd_tcp
   A.close_all = opts->close_all;
   A.recs = recs;
   A.streams = streams;
-  A.bytes = bytes;
   // scratch sized by the hand-off: result words, page ids, block sums, the groups' counts and streams
   const uint32_t nblk_s = (A.cnt + kCompactBlock - 1u) / kCompactBlock;
   const uint32_t nblk_g = (A.ng + kCompactBlock - 1u) / kCompactBlock;
@@ -415,12 +318,12 @@ extern "C" int gpd_tcp_assemble(gpd_ctx *ctx, const gpd_batch *in, const gpd_tcp
   if (!base) return set_error(GPD_ERR_NOMEM, "%s: scratch allocation failed", who);
   carve(base);
   A.nblk = nblk_s;
-  TA_TRY(hipMemsetAsync(A.res, 0, b_res, s));
+  GPD_TRY(hipMemsetAsync(A.res, 0, b_res, s));
   hipLaunchKernelGGL(ta_pages_sum_kernel, dim3(nblk_s), dim3(256), 0, s, A);
-  TA_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint64_t npages = 0;
-  TA_TRY(hipMemcpyAsync(&npages, A.res + 4, 8, hipMemcpyDeviceToHost, s));
-  TA_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(&npages, A.res + 4, 8, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   if (npages > 0xFFFFFFFFull)
     return set_error(GPD_ERR_INVALID, "%s: %llu pages (max 2^32 - 1)", who, (unsigned long long)npages);
   // the page arrays: nodes and private records, 32 bytes each per page.  Growing the slot
@@ -430,7 +333,7 @@ extern "C" int gpd_tcp_assemble(gpd_ctx *ctx, const gpd_batch *in, const gpd_tcp
     base = static_cast<uint8_t *>(ctx_scratch(ctx, 17, fixed + 2 * b_pages));
     if (!base) return set_error(GPD_ERR_NOMEM, "%s: scratch allocation failed", who);
     carve(base);
-    TA_TRY(hipMemsetAsync(A.res, 0, b_res, s));
+    GPD_TRY(hipMemsetAsync(A.res, 0, b_res, s));
     hipLaunchKernelGGL(ta_pages_sum_kernel, dim3(nblk_s), dim3(256), 0, s, A);
   }
   A.nodes = reinterpret_cast<TsmNode *>(base + fixed);
@@ -444,10 +347,10 @@ extern "C" int gpd_tcp_assemble(gpd_ctx *ctx, const gpd_batch *in, const gpd_tcp
   hipLaunchKernelGGL(ta_scan_kernel, dim3(3), dim3(1024), 0, s, A);
   hipLaunchKernelGGL(ta_group_apply_kernel, dim3(nblk_g, 2), dim3(256), 0, s, A);
   hipLaunchKernelGGL(ta_totals_kernel, dim3(1), dim3(64), 0, s, A);
-  TA_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint64_t tot[4] = {0, 0, 0, 0};
-  TA_TRY(hipMemcpyAsync(tot, A.res, 32, hipMemcpyDeviceToHost, s));
-  TA_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(tot, A.res, 32, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   for (int k = 0; k < 4; ++k) out[k] = tot[k];
   if (!recs && !max_recs) return GPD_OK;  // the sizing call
   const bool gather = bytes != nullptr || max_bytes != 0;
@@ -457,15 +360,16 @@ extern "C" int gpd_tcp_assemble(gpd_ctx *ctx, const gpd_batch *in, const gpd_tcp
   if (gather && tot[2] > max_bytes)
     return set_error(GPD_ERR_INVALID, "%s: %llu bytes, max_bytes is %llu", who, (unsigned long long)tot[2],
                      (unsigned long long)max_bytes);
-  A.nrecs = (uint32_t)tot[0];
-  A.nbytes = tot[2];
   hipLaunchKernelGGL(ta_place_kernel, dim3(wgrid), dim3(64 * kWalkWaves), 0, s, A);
-  if (gather && A.nrecs && A.nbytes) {
-    const uint32_t nwave = (A.nrecs + 63u) / 64u;
-    hipLaunchKernelGGL(ta_gather_kernel, dim3((nwave + kGatherWaves - 1u) / kGatherWaves), dim3(64 * kGatherWaves), 0,
-                       s, A);
+  if (gather) {
+    RecSource G{};
+    G.set(0, in->data, in->data_len);
+    G.recs = recs;
+    G.offset = in->offset;
+    G.n = (uint32_t)in->n;
+    launch_gather(G, (uint32_t)tot[0], bytes, tot[2], s);
   }
-  TA_TRY(hipGetLastError());
-  TA_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipGetLastError());
+  GPD_TRY(hipStreamSynchronize(s));
   return GPD_OK;
 }

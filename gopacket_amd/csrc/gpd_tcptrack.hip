@@ -243,19 +243,10 @@ __global__ __launch_bounds__(256) void tk_forget_kernel(uint8_t *carried, uint32
     if (ids[k] < cap) carried[ids[k]] = 0;
 }
 
-#define TK_TRY(expr)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return gpd::set_error(GPD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));           \
-  } while (0)
-
-inline size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-
 // The object's scratch buffer `buf` with at least `bytes` (its contents are not kept).
 int grow(uint8_t *&buf, size_t &have, size_t bytes, const char *who) {
   if (have >= bytes) return GPD_OK;
-  if (buf) TK_TRY(hipFree(buf));
+  if (buf) GPD_TRY(hipFree(buf));
   buf = nullptr;
   have = 0;
   if (hipMalloc(reinterpret_cast<void **>(&buf), bytes) != hipSuccess) {
@@ -273,7 +264,7 @@ int need_carry(gpd_tcp_tracker *t, const char *who) {
     t->carried = nullptr;
     return set_error(GPD_ERR_NOMEM, "%s: state allocation failed", who);
   }
-  TK_TRY(hipMemset(t->carried, 0, t->cap));
+  GPD_TRY(hipMemset(t->carried, 0, t->cap));
   return GPD_OK;
 }
 
@@ -331,7 +322,7 @@ extern "C" int gpd_tcp_tracker_run(gpd_tcp_tracker *t, const gpd_batch *in, cons
   if (!res->hdr_off || (!res->records && !res->status))
     return set_error(GPD_ERR_INVALID, "%s: needs hdr_off and status (or records)", who);
   DeviceScope dscope_;
-  TK_TRY(dscope_.set(t->device));
+  GPD_TRY(dscope_.set(t->device));
   const hipStream_t s = (hipStream_t)stream;
   int rc = need_carry(t, who);
   if (rc != GPD_OK) return rc;
@@ -356,13 +347,13 @@ extern "C" int gpd_tcp_tracker_run(gpd_tcp_tracker *t, const gpd_batch *in, cons
   A.blk = reinterpret_cast<uint32_t *>(t->sa + 16);
   A.mask = reinterpret_cast<uint64_t *>(t->sa + 16 + b_blk);
   A.idx = reinterpret_cast<uint32_t *>(t->sa + 16 + b_blk + b_mask);
-  TK_TRY(hipMemsetAsync(A.tally, 0, 16, s));
+  GPD_TRY(hipMemsetAsync(A.tally, 0, 16, s));
   hipLaunchKernelGGL(tk_count_kernel, dim3(A.nblk), dim3(256), 0, s, A);
   hipLaunchKernelGGL(tk_scan_kernel, dim3(1), dim3(1024), 0, s, A);
-  TK_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   uint32_t total = 0;
-  TK_TRY(hipMemcpyAsync(&total, A.blk + A.nblk, 4, hipMemcpyDeviceToHost, s));
-  TK_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(&total, A.blk + A.nblk, 4, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   if (total == 0) return GPD_OK;
   A.cnt = total;
   hipLaunchKernelGGL(tk_index_kernel, dim3(A.nblk), dim3(64), 0, s, A);
@@ -382,7 +373,7 @@ extern "C" int gpd_tcp_tracker_run(gpd_tcp_tracker *t, const gpd_batch *in, cons
   A.agg_f = reinterpret_cast<uint32_t *>(t->sb + 2 * b_pair + b_info + b_hist + 2 * b_m);
   const PeerArgs Q{in->data, in->data_len, in->offset, res->status, res->hdr_off, res->records,
                    flow_id, A.idx, total, t->carried, pa, info, conn_id};
-  TK_TRY(launch_flow_peers(t->ft, Q, s));
+  GPD_TRY(launch_flow_peers(t->ft, Q, s));
   const SortArgs S{total, stile, hist};
   const uint32_t passes = sort_passes(t->cap - 1u);  // c < capacity
   const uint2 *src = sort_leading_passes(S, pa, pb, passes, s);
@@ -391,10 +382,10 @@ extern "C" int gpd_tcp_tracker_run(gpd_tcp_tracker *t, const gpd_batch *in, cons
   hipLaunchKernelGGL(tk_tile_kernel<false>, dim3(A.ntile), dim3(kTrkThreads), 0, s, A, sorted);
   hipLaunchKernelGGL(tk_agg_kernel, dim3(1), dim3(kAggRound), 0, s, A);
   hipLaunchKernelGGL(tk_tile_kernel<true>, dim3(A.ntile), dim3(kTrkThreads), 0, s, A, sorted);
-  TK_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   unsigned long long tally[2] = {0, 0};
-  TK_TRY(hipMemcpyAsync(tally, A.tally, 16, hipMemcpyDeviceToHost, s));
-  TK_TRY(hipStreamSynchronize(s));
+  GPD_TRY(hipMemcpyAsync(tally, A.tally, 16, hipMemcpyDeviceToHost, s));
+  GPD_TRY(hipStreamSynchronize(s));
   out[0] = total;
   out[1] = tally[0];
   out[2] = total - tally[0];
@@ -407,10 +398,10 @@ extern "C" int gpd_tcp_tracker_states(gpd_tcp_tracker *t, uint8_t *out, void *st
   const char *who = "gpd_tcp_tracker_states";
   if (!t || !out) return set_error(GPD_ERR_INVALID, "%s: null argument", who);
   DeviceScope dscope_;
-  TK_TRY(dscope_.set(t->device));
+  GPD_TRY(dscope_.set(t->device));
   const int rc = need_carry(t, who);
   if (rc != GPD_OK) return rc;
-  TK_TRY(hipMemcpyAsync(out, t->carried, t->cap, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  GPD_TRY(hipMemcpyAsync(out, t->carried, t->cap, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return GPD_OK;
 }
 
@@ -420,10 +411,10 @@ extern "C" int gpd_tcp_tracker_forget(gpd_tcp_tracker *t, const uint32_t *ids, u
   if (!t || (m && !ids)) return set_error(GPD_ERR_INVALID, "%s: null argument", who);
   if (m == 0 || !t->carried) return GPD_OK;  // (nothing carried yet: every connection is fresh)
   DeviceScope dscope_;
-  TK_TRY(dscope_.set(t->device));
+  GPD_TRY(dscope_.set(t->device));
   const unsigned grid = (unsigned)std::min<uint64_t>((m + 255u) / 256u, (uint64_t)std::max(t->num_cus, 1) * 8u);
   hipLaunchKernelGGL(tk_forget_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, t->carried, t->cap, ids, m);
-  TK_TRY(hipGetLastError());
+  GPD_TRY(hipGetLastError());
   return GPD_OK;
 }
 
@@ -432,7 +423,7 @@ extern "C" int gpd_tcp_tracker_reset(gpd_tcp_tracker *t, void *stream) {
   if (!t) return set_error(GPD_ERR_INVALID, "gpd_tcp_tracker_reset: null argument");
   if (!t->carried) return GPD_OK;
   DeviceScope dscope_;
-  TK_TRY(dscope_.set(t->device));
-  TK_TRY(hipMemsetAsync(t->carried, 0, t->cap, (hipStream_t)stream));
+  GPD_TRY(dscope_.set(t->device));
+  GPD_TRY(hipMemsetAsync(t->carried, 0, t->cap, (hipStream_t)stream));
   return GPD_OK;
 }

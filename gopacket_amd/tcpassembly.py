@@ -32,7 +32,7 @@ assert SEG_DTYPE.itemsize == 32 and GROUP_DTYPE.itemsize == 16
 TCP_UNGROUPED = 0xFFFFFFFF
 # flags bits (header bytes 12..13 & 0x1FF)
 TCP_FIN, TCP_SYN, TCP_RST, TCP_PSH, TCP_ACK, TCP_URG, TCP_ECE, TCP_CWR, TCP_NS = (1 << b for b in range(9))
-# pairs one workgroup of the sort's scatter ranks (gpd_tcpseg.hip kSortTile)
+# pairs one workgroup of the sort's scatter ranks (gpd_radix_sort.h kSortTile)
 SORT_TILE = 8192
 
 TCPSEG_EXPORTS = {

@@ -18,9 +18,9 @@ from gopacket_amd.batch import PAD, PacketBatch
 # ---- the kernels' constants -------------------------------------------------------------------
 COMPACT_BLOCK = 2048                        # gpd_compact.h:18 kCompactBlock
 COMPACT_ROUND = 1024 * COMPACT_BLOCK        # gpd_compact.h:56 `c0 += 1024u` block counts a round
-SORT_TILE = 8192                            # gpd_tcpseg.hip:51 kSortTile (tcpassembly.SORT_TILE)
-SORT_ROUND = 16384 // 256 * SORT_TILE       # gpd_tcpseg.hip:258 `c0 += 16384u` of hist[256][ntile];
-#                                             gpd_ip4reasm.hip is_scan_kernel is the same scan
+SORT_TILE = 8192                            # gpd_radix_sort.h:30 kSortTile (tcpassembly.SORT_TILE)
+SORT_ROUND = 16384 // 256 * SORT_TILE       # gpd_radix_sort.h:32 kSortScanRound of hist[256][ntile]: the
+#                                             one scan of the hand-off, the tracker and reassembly
 WRITE_BLOCK = 1024                          # gpd_pcapwrite.hip:47, gpd_pcapngwrite.hip:53 kScanBlock
 WRITE_ROUND = 1024 * WRITE_BLOCK            # gpd_pcapwrite.hip:185, gpd_pcapngwrite.hip:186 `c * 1024u + t`
 

@@ -117,6 +117,28 @@ def test_random_groups(parser):
     p.close()
 
 
+@pytest.mark.parametrize("n", [255, 256])
+def test_sort_pass_count_step(parser, n):
+    """A fresh defragmenter (no carried lists, so the sort's items are the n records) with 255 and
+    with 256 records: gpd_radix_sort.h's sort_passes(n) goes from 1 (the last pass alone, with
+    reassembly's sink) to 2 (a leading pass, then the last).  Datagrams of 2 and 3 fragments under
+    distinct keys, every fifth without its last fragment, interleaved."""
+    rng = np.random.default_rng(70 + n)
+    groups, left = [], n
+    while left:
+        k = len(groups)
+        g = in_order(rng, 2 + k % 2, hi=3)
+        g = g[:min(len(g) - (k % 5 == 4), left)]
+        groups.append(frames_of(rng, g, key_of(k)))
+        left -= len(g)
+    p = Pair(parser)
+    h, e = p.feed(interleave(rng, groups))
+    assert len(h.outcomes) == n and set(h.outcomes["what"]) == {RR.FILED, RR.COMPLETE}
+    assert set(h.dgrams["nfrags"]) == {2, 3} and len(h.dgrams) > 60
+    assert p.dev.stats()["lists"] >= len(groups) // 5
+    p.close()
+
+
 # ---------------------------------------------------------------- 3. the in-order run's edges
 def _eights(n, first=0, last_mf=False):
     return [spec(8 * k, 8, last_mf or k != n - 1) for k in range(first, n)]

@@ -412,17 +412,15 @@ def reasm_periods(parser):
 
 @pytest.mark.parametrize("k", range(6))
 def test_reassembly_past_the_first_round(parser, reasm_periods, k):
-    """is_scan_kernel (the sort's histogram scan over M = carried lists + records: a round is 64
-    tiles) at the first three sizes, ir_scan_kernel (compact_scan over the head flags of the M
-    items, then the records' and the groups' block sums, three arrays each) at the last three.
+    """sort_scan_kernel (gpd_radix_sort.h, the sort's histogram scan over M = carried lists +
+    records: a round is 64 tiles) at the first three sizes, ir_scan_kernel (compact_scan over the
+    head flags of the M items, then the records' and the groups' block sums, three arrays each) at
+    the last three.
     Call 1 takes n records of datagrams of 2, 3 and 8 fragments, every replica under a key of its
     own, and leaves three lists in four carried; call 2 completes the lists of the first, a middle
     and the last replica from a store that was built past the round, with M = the carried lists
     + its records.  Outcomes, datagram records, offsets, lengths, bytes and stats() against the
     oracle's, tiled."""
-    from gopacket_amd import ip4reasm as I
-    from gopacket_amd import parser as P
-    (f1, r1, e1, st1), (f2, r2, e2, st2), (fu, ru, eu, stu) = reasm_periods
     n = I_SIZES[k]
     if k < 3:
         assert RC.rounds(256 * ((n + RC.SORT_TILE - 1) // RC.SORT_TILE), 16384) == k + 1
@@ -430,6 +428,23 @@ def test_reassembly_past_the_first_round(parser, reasm_periods, k):
     else:
         assert RC.rounds((n + RC.COMPACT_BLOCK - 1) // RC.COMPACT_BLOCK, 1024) == k - 2
         assert k < 5 or n > 2 * RC.COMPACT_ROUND
+    _reasm_two_calls(parser, reasm_periods, n, k)
+
+
+@pytest.mark.parametrize("n", [65535, 65536])
+def test_reassembly_at_the_three_pass_step(parser, reasm_periods, n):
+    """The same two calls on a fresh defragmenter at M = 65,535 and 65,536 items, where the sort's
+    keys [0, M] go from 16 to 17 bits: two passes (one leading pass and the last) become three.
+    Every size of test_reassembly_past_the_first_round lies above the step (M >= 524,288 in call 1
+    and more than 65,536 carried lists in call 2: three passes); the one- and two-pass sorts are
+    test_ip4reasm_gpu.py's (255, 256, 8,184 and 8,193 records)."""
+    _reasm_two_calls(parser, reasm_periods, n, None)
+
+
+def _reasm_two_calls(parser, reasm_periods, n, k):
+    from gopacket_amd import ip4reasm as I
+    from gopacket_amd import parser as P
+    (f1, r1, e1, st1), (f2, r2, e2, st2), (fu, ru, eu, stu) = reasm_periods
     reps, unit = n // len(f1), n % len(f1)
     main_ids, unit_ids = np.arange(reps), reps + np.arange(unit)
     dev = I.NewIPv4Defragmenter(parser)

@@ -111,12 +111,45 @@ def test_lazy_reexport_and_build_lists():
 
 
 def test_sort_has_one_copy():
-    """The sort kernels live in gpd_radix_sort.h alone; both users include it."""
+    """The sort kernels live in gpd_radix_sort.h alone; its three users include it."""
     csrc = os.path.join(ROOT, "gopacket_amd", "csrc")
-    for f in ("gpd_tcpseg.hip", "gpd_tcptrack.hip"):
+    for f in ("gpd_tcpseg.hip", "gpd_tcptrack.hip", "gpd_ip4reasm.hip"):
         text = open(os.path.join(csrc, f)).read()
         assert '#include "gpd_radix_sort.h"' in text and "void sort_scatter_kernel" not in text, f
+        assert not re.search(r"void\s+\w*_scatter_kernel\b", text), f  # no scatter kernel of its own
+        assert not re.search(r"\bmatch_digit\b|\bkSortTile\s*=", text), f
     assert open(os.path.join(csrc, "gpd_radix_sort.h")).read().count("void sort_scatter_kernel") == 1
+
+
+def _csrc_texts():
+    csrc = os.path.join(ROOT, "gopacket_amd", "csrc")
+    return {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))
+            if f.endswith((".h", ".hip", ".cpp"))}
+
+
+def test_gather_has_one_copy():
+    """The 16-byte gather's chunk loop is one kernel, in gpd_gather.h; the three stream stages
+    include it and none defines a __global__ gather of its own (the stream assembly's is folded in
+    too: there is no fallback kernel)."""
+    texts = _csrc_texts()
+    defs = {f: re.findall(r"__global__[^;{]*?\b(\w*gather\w*)\s*\(", t) for f, t in texts.items()}
+    assert {f: d for f, d in defs.items() if d} == {"gpd_gather.h": ["gather_kernel"]}
+    for f in ("gpd_ip4reasm.hip", "gpd_tcpasm.hip", "gpd_tcpstream.hip"):
+        assert '#include "gpd_gather.h"' in texts[f], f
+        assert not re.search(r"struct\s+(GRec|GaArgs|GatherRec)\b|kGatherWaves\s*=|__builtin_nontemporal_store", texts[f]), f
+    from gopacket_amd.build import HEADERS
+    assert "gpd_gather.h" in {os.path.basename(h) for h in HEADERS}
+
+
+def test_host_helpers_have_one_copy():
+    """One error-return macro per message format (GPD_TRY in gpd_internal.h, HIP_TRY in
+    gpd_ctx.h), one up16 and one grow."""
+    texts = _csrc_texts()
+    macros = {f: re.findall(r"#\s*define\s+(\w*_TRY)\s*\(", t) for f, t in texts.items()}
+    assert {f: m for f, m in macros.items() if m} == {"gpd_ctx.h": ["HIP_TRY"], "gpd_internal.h": ["GPD_TRY"]}
+    assert '"%s: %s", #expr' in texts["gpd_internal.h"] and '"%s failed: %s", #expr' in texts["gpd_ctx.h"]
+    for pat in (r"\bsize_t\s+up16\s*\(", r"\bbool\s+grow\s*\("):
+        assert {f: len(re.findall(pat, t)) for f, t in texts.items() if re.search(pat, t)} == {"gpd_internal.h": 1}, pat
 
 
 def test_struct_layouts_and_constants_match_c(tmp_path):
