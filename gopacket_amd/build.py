@@ -58,6 +58,7 @@ HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h")
            os.path.join(ROOT, "include", "gpd_tcpasm.h"), os.path.join(CSRC, "gpd_tcpasm_walk.h"),
            os.path.join(ROOT, "include", "gpd_tcptrack.h"), os.path.join(CSRC, "gpd_tcptrack_fsm.h"),
            os.path.join(CSRC, "gpd_radix_sort.h"), os.path.join(CSRC, "gpd_gather.h"),
+           os.path.join(CSRC, "gpd_write_scan.h"),
            os.path.join(ROOT, "include", "gpd_flow_expire.h"), os.path.join(CSRC, "gpd_flow_slots.h")]
 
 

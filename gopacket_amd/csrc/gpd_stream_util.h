@@ -1,7 +1,8 @@
 // gpd_stream_util.h — device helpers the stream builders share (gpd_tcpstream.hip,
 // gpd_ip4reasm.hip, gpd_tcpasm.hip): the two-level scan over an array of per-item values (block
 // sums, gpd_compact.h's compact_scan over them, the prefix per item) and the byte shuffles of the
-// 16-byte gather (gpd_gather.h).  No kernel here waits on another workgroup.
+// 16-byte gather (gpd_gather.h).  The two writers (gpd_write_scan.h) take the byte shuffles and
+// the 64-bit wave helpers from here too.  No kernel here waits on another workgroup.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,6 +67,24 @@ __device__ __forceinline__ uint32_t first_lane(uint32_t v) { return (uint32_t)__
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
   const uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
   return ((uint64_t)hi << 32) | lo;
+}
+__device__ inline uint64_t shfl_up64(uint64_t v, uint32_t d) {
+  const uint32_t lo = __shfl_up((uint32_t)v, d, 64), hi = __shfl_up((uint32_t)(v >> 32), d, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+// inclusive scan across the wave
+__device__ inline uint64_t wave_scan64(uint64_t v, uint32_t lane) {
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const uint64_t y = shfl_up64(v, d);
+    if (lane >= d) v += y;
+  }
+  return v;
+}
+__device__ inline uint32_t wave_min32(uint32_t v) {
+#pragma unroll
+  for (uint32_t d = 32; d >= 1u; d >>= 1) v = min(v, (uint32_t)__shfl_xor(v, d, 64));
+  return v;
 }
 
 // ---- the gather, 16 bytes at a time -------------------------------------------------------------

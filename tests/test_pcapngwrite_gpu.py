@@ -2,12 +2,12 @@
 comparison is exact equality, and every output buffer is carved from a larger one filled with
 0xA5 whose bytes at or beyond the reported length must survive the call.
 
-The scan's workgroup takes SCAN_BLOCK packets (kScanBlock, gpd_pcapngwrite.hip) and the kernel
+The scan's workgroup takes SCAN_BLOCK packets (kScanBlock, gpd_write_scan.h) and the kernel
 that scans the block totals takes 1024 of them per round, so the sizes at which the code takes
 another path are 64 (a wave), SCAN_BLOCK, and 1024 * SCAN_BLOCK packets.  A record is a multiple
 of 4 bytes, so the first record starts at prefix_len mod 16 in {0, 4, 8, 12}.
 
-On the input side the bounds are checked by reading the code (src16 issues a load only where it
+On the input side the bounds are checked by reading the code (src16_of issues a load only where it
 starts inside [0, round_up(data_len, 16))); the "end" layout documents the case.
 """
 import ctypes as C
@@ -337,6 +337,32 @@ def test_scan_carry_beyond_1024_blocks():
     keep[-1] = 1                  # ... and is the second round's only one
     d = Dev(b, rng.integers(0, 1 << 64, n, dtype=np.uint64))
     d.check_write(keep, 1, PREFIXES[1])
+
+
+def test_next_kept_record_whole_blocks_away():
+    """The three record forms on one batch of 3 * SCAN_BLOCK packets of 5 bytes (a pcap record is
+    21 bytes, a pcapng record 40: a run of one record ends inside a chunk).  Only packets 1023 and
+    2048 are kept: block 1 is empty, so the header that completes the last chunk of block 0's run
+    is found through the block's next-kept index, not through a later wave of the block.  With
+    1023 alone there is no next record and that chunk is the stream's ragged end."""
+    from test_pcapwrite_gpu import FILE_HEADER, Dev as PcapDev
+    n = 3 * SCAN_BLOCK
+    b, rng = _batch(n, 12, lens=[5] * n)
+    ts = rng.integers(0, 1 << 62, n).astype(np.uint64)
+    blocks = (R.section_block(b"amd64", b"linux", b"gopacket") + R.interface_block(1, 0, b"intf0", os_=b"linux") +
+              R.interface_block(1, 0, b"intf1"))  # a section and two interfaces: records start at 8 mod 16
+    assert len(blocks) == 168 and len(PREFIXES[1]) == 4
+    pc, ng = PcapDev(b, ts), Dev(b, ts)
+    for kept in ((1023, 2048), (1023,)):
+        keep = np.zeros(n, np.uint8)
+        keep[list(kept)] = 1
+        for flags in (0, FILE_HEADER):
+            ref = pc.check_write(keep, flags, (65535, 1))
+            assert len(ref) == (24 if flags else 0) + 21 * len(kept)
+        pc.check_select(keep)
+        for prefix in (blocks, PREFIXES[1]):
+            ref = ng.check_write(keep, 1, prefix)
+            assert len(ref) == len(prefix) + 40 * len(kept)
 
 
 # ---- 8. end to end ---------------------------------------------------------------------------------

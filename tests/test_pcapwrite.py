@@ -5,6 +5,8 @@ import ctypes as C
 import io
 import json
 import os
+import re
+import subprocess
 
 import pytest
 
@@ -12,6 +14,7 @@ import pcapwrite_ref as WR
 from gopacket_amd import pcap
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
 VEC = json.load(open(os.path.join(HERE, "golden", "pcapgo_write_vectors.json")))
 CAPTURES = ["test_dns.pcap", "test_ethernet.pcap", "test_loopback.pcap"]
 
@@ -118,3 +121,73 @@ def test_new_symbols_exported_and_abi_version_kept():
 def test_lazy_reexport():
     import gopacket_amd
     assert gopacket_amd.pcapwrite.NewWriter is not None
+
+
+def test_host_error_paths_under_host_sanitizers(tmp_path):
+    """tests/c/pcapwrite_errpath.cpp: a stand-alone program (its own main, the runtime stubbed)
+    linked with gpd_pcapwrite.hip alone, host code built with AddressSanitizer and UBSan, run on
+    the CPU: gpd_pcap_file_header, and every path of gpd_pcap_write and gpd_batch_select that
+    returns before a device is needed, error texts compared whole."""
+    from gopacket_amd.build import ARCH, CSRC, HIPCC
+    exe = tmp_path / "pcapwrite_errpath"
+    subprocess.run([HIPCC, f"--offload-arch={ARCH}", "-std=c++17", "-O1", "-g", "-I", os.path.join(ROOT, "include"),
+                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                    os.path.join(ROOT, "tests", "c", "pcapwrite_errpath.cpp"),
+                    os.path.join(CSRC, "gpd_pcapwrite.hip"), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", (r.stdout, r.stderr)
+
+
+# ---------------------------------------------------------------- one scan, one chunk loop
+WRITERS = ("gpd_pcapwrite.hip", "gpd_pcapngwrite.hip")
+
+
+def _csrc_texts():
+    csrc = os.path.join(ROOT, "gopacket_amd", "csrc")
+    return {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))
+            if f.endswith((".h", ".hip", ".cpp"))}
+
+
+def test_wave_and_byte_helpers_have_one_copy():
+    """The byte shuffles, the 64-bit wave helpers and check_in are each defined once in
+    gopacket_amd/csrc: the helpers in gpd_stream_util.h, check_in in gpd_write_scan.h."""
+    texts = _csrc_texts()
+    where = {"bytes_from": "gpd_stream_util.h", "byte_mask": "gpd_stream_util.h", "low_bytes": "gpd_stream_util.h",
+             "wave_scan64": "gpd_stream_util.h", "shfl64": "gpd_stream_util.h", "shfl_up64": "gpd_stream_util.h",
+             "wave_min32": "gpd_stream_util.h", "src16_of": "gpd_stream_util.h"}
+    for name, home in where.items():
+        pat = r"^[ \t]*(?:static\s+)?__device__[^;{()]*\b%s\s*\([^;{]*\)\s*\{" % name
+        assert {f: len(re.findall(pat, t, re.M)) for f, t in texts.items() if re.search(pat, t, re.M)} == {home: 1}, name
+    pat = r"\bint check_in\s*\("
+    assert {f: len(re.findall(pat, t)) for f, t in texts.items() if re.search(pat, t)} == {"gpd_write_scan.h": 1}
+    for f in WRITERS:
+        assert not re.search(r"\bsrc16\s*\(|\bshfl64\s*\([^)]*\)\s*\{", texts[f]), f
+
+
+def test_scan_and_chunk_loop_have_one_copy():
+    """The full form: bad, sum, scan and copy kernels live in gpd_write_scan.h alone, one
+    __global__ copy kernel for the three record forms; the writers include the header, define
+    their forms and neither kept() nor a kernel of those kinds of their own."""
+    texts = _csrc_texts()
+    kernels = lambda t: re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", t)
+    assert sorted(kernels(texts["gpd_write_scan.h"])) == ["bad_kernel", "copy_kernel", "scan_kernel", "sum_kernel"]
+    assert kernels(texts["gpd_pcapwrite.hip"]) == ["pw_head_kernel"] and kernels(texts["gpd_pcapngwrite.hip"]) == []
+    copies = {f: [k for k in kernels(t) if "copy" in k] for f, t in texts.items()}
+    assert {f: c for f, c in copies.items() if c} == {"gpd_write_scan.h": ["copy_kernel"]}
+    for f in WRITERS:
+        t = texts[f]
+        assert '#include "gpd_write_scan.h"' in t, f
+        assert not re.search(r"\bbool\s+kept\s*\(|struct\s+(WrArgs|NgwArgs|Rec)\b|__builtin_nontemporal_store", t), f
+        assert not re.search(r"GPD_PW_(COPY_WAVES|NT_LOADS|PLAIN_STORES)", t), f
+        assert not re.search(r"\bk(ScanBlock|ScanWaves|CopyWaves|None)\s*=", t), f
+    assert re.findall(r"struct\s+(\w+Form)\b", texts["gpd_pcapwrite.hip"]) == ["PcapForm", "BatchForm"]
+    assert re.findall(r"struct\s+(\w+Form)\b", texts["gpd_pcapngwrite.hip"]) == ["NgForm"]
+    for form in ("PcapForm", "BatchForm"):
+        assert f"copy_kernel<{form}>" in texts["gpd_pcapwrite.hip"] and f"sum_kernel<{form}>" in texts["gpd_pcapwrite.hip"]
+    assert "copy_kernel<NgForm>" in texts["gpd_pcapngwrite.hip"] and "sum_kernel<NgForm>" in texts["gpd_pcapngwrite.hip"]
+    assert "kCopyWaves = 4;" in texts["gpd_write_scan.h"]
+    assert "GPD_PW_" not in texts["gpd_write_scan.h"]
+    from gopacket_amd.build import HEADERS
+    assert "gpd_write_scan.h" in {os.path.basename(h) for h in HEADERS}
+    from gopacket_amd import _lib
+    assert _lib.lib.gpd_abi_version() == 10

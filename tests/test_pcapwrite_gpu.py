@@ -2,11 +2,11 @@
 every comparison is exact equality, and every output buffer is carved from a larger one filled
 with 0xA5 whose bytes at or beyond the reported length must survive the call.
 
-The scan's workgroup takes SCAN_BLOCK packets (kScanBlock, gpd_pcapwrite.hip) and the kernel
+The scan's workgroup takes SCAN_BLOCK packets (kScanBlock, gpd_write_scan.h) and the kernel
 that scans the block totals takes 1024 of them per round, so the sizes at which the code takes
 another path are 64 (a wave), SCAN_BLOCK, and 1024 * SCAN_BLOCK packets.
 
-On the input side the bounds are checked by reading the code (src16 issues a load only where it
+On the input side the bounds are checked by reading the code (src16_of issues a load only where it
 starts inside [0, round_up(data_len, 16))); the "end" layout documents the case: its last packet
 ends exactly at data_len and the device buffer ends at round_up(data_len, 16).
 """
@@ -219,6 +219,21 @@ def test_shape_sweep(n, layout):
         for flags in (0, NANOS, FILE_HEADER, NANOS | FILE_HEADER):  # records start at 0 and at 8 mod 16
             d.check_write(keep, flags, (262144, 1), use_length=(name != "ones"))
         d.check_select(keep)
+
+
+@pytest.mark.parametrize("n", [SCAN_BLOCK - 1, SCAN_BLOCK, SCAN_BLOCK + 1])
+def test_scan_block_edge(n):
+    """One block, one block exactly, and a second block of one packet (COUNTS steps from 65 to
+    4097).  The selection reads the shared scan's block and wave prefixes of the kept counts."""
+    b = _sweep_batch(n, "packed1")
+    rng = np.random.default_rng(n + 6)
+    ts = rng.integers(0, 1 << 62, n).astype(np.uint64)
+    d = Dev(b, ts, b.caplen + rng.integers(0, 3, n).astype(np.uint32))
+    masks = _masks(n)
+    for name in ("null", "alternating", "last"):
+        for flags in (0, FILE_HEADER):
+            d.check_write(masks[name], flags, (262144, 1))
+        d.check_select(masks[name])
 
 
 def test_scan_carry_beyond_1024_blocks():

@@ -122,7 +122,7 @@ def _prove_writer_expectation(w, fmt, keep):
 
 @pytest.mark.parametrize("k,mask,fmt", [(k, m, f) for k, m in W_CASES for f in ("pcap", "pcapng")])
 def test_writer_block_totals_past_the_first_round(parser, k, mask, fmt):
-    """pw_scan_kernel / ngw_scan_kernel: the forward carries of positions and counts into the
+    """scan_kernel (gpd_write_scan.h, both writers): the forward carries of positions and counts into the
     second and third chunk of 1024 block totals, and `mcarry`, the first kept packet of any later
     chunk, backwards ("round2": across two chunks; "last": from the stream's last packet).  "bad":
     a kept packet with length < capture length in the third round cuts the stream there."""

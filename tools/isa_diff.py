@@ -1,4 +1,4 @@
-"""Compare the decode kernels' and the pcap writer's device code between two source trees, kernel
+"""Compare the decode kernels' and the two writers' device code between two source trees, kernel
 by kernel:
     python tools/isa_diff.py OLD_TREE NEW_TREE [--diag] [-DFLAG ...]
 Each tree's kernel translation units (whichever of KERNEL_TUS it has) are compiled to gfx950
@@ -17,7 +17,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFILT = os.environ.get("CXXFILT", "c++filt")
-KERNEL_TUS = ["gpd_kernels.hip", "gpd_rs.hip", "gpd_ro.hip", "gpd_sp.hip", "gpd_pcapwrite.hip"]
+KERNEL_TUS = ["gpd_kernels.hip", "gpd_rs.hip", "gpd_ro.hip", "gpd_sp.hip", "gpd_pcapwrite.hip",
+              "gpd_pcapngwrite.hip"]
 
 
 def kernel_tus(tree):
