@@ -38,7 +38,8 @@ SOURCES = [*KERNEL_SOURCES, os.path.join(CSRC, "gpd_runtime.cpp"),
            os.path.join(CSRC, "gpd_bpf.hip"), os.path.join(CSRC, "gpd_bpf_host.cpp"),
            os.path.join(CSRC, "gpd_tcpseg.hip"), os.path.join(CSRC, "gpd_pcapngwrite.hip"),
            os.path.join(CSRC, "gpd_tcpstream.hip"), os.path.join(CSRC, "gpd_ip4reasm.hip"),
-           os.path.join(CSRC, "gpd_tcpasm.hip"), os.path.join(CSRC, "gpd_tcptrack.hip")]
+           os.path.join(CSRC, "gpd_tcpasm.hip"), os.path.join(CSRC, "gpd_tcptrack.hip"),
+           os.path.join(CSRC, "gpd_dns.hip")]
 HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h"),
            os.path.join(CSRC, "gpd_segwalk.h"), os.path.join(CSRC, "gpd_launch.h"),
            os.path.join(CSRC, "gpd_compact.h"),
@@ -59,7 +60,8 @@ HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h")
            os.path.join(ROOT, "include", "gpd_tcptrack.h"), os.path.join(CSRC, "gpd_tcptrack_fsm.h"),
            os.path.join(CSRC, "gpd_radix_sort.h"), os.path.join(CSRC, "gpd_gather.h"),
            os.path.join(CSRC, "gpd_write_scan.h"),
-           os.path.join(ROOT, "include", "gpd_flow_expire.h"), os.path.join(CSRC, "gpd_flow_slots.h")]
+           os.path.join(ROOT, "include", "gpd_flow_expire.h"), os.path.join(CSRC, "gpd_flow_slots.h"),
+           os.path.join(ROOT, "include", "gpd_dns.h"), os.path.join(CSRC, "gpd_dns_walk.h")]
 
 
 def _stale(target, deps):
