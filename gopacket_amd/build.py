@@ -39,7 +39,7 @@ SOURCES = [*KERNEL_SOURCES, os.path.join(CSRC, "gpd_runtime.cpp"),
            os.path.join(CSRC, "gpd_tcpseg.hip"), os.path.join(CSRC, "gpd_pcapngwrite.hip"),
            os.path.join(CSRC, "gpd_tcpstream.hip"), os.path.join(CSRC, "gpd_ip4reasm.hip"),
            os.path.join(CSRC, "gpd_tcpasm.hip"), os.path.join(CSRC, "gpd_tcptrack.hip"),
-           os.path.join(CSRC, "gpd_dns.hip")]
+           os.path.join(CSRC, "gpd_dns.hip"), os.path.join(CSRC, "gpd_tls.hip")]
 HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h"),
            os.path.join(CSRC, "gpd_segwalk.h"), os.path.join(CSRC, "gpd_launch.h"),
            os.path.join(CSRC, "gpd_compact.h"),
@@ -61,7 +61,9 @@ HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h")
            os.path.join(CSRC, "gpd_radix_sort.h"), os.path.join(CSRC, "gpd_gather.h"),
            os.path.join(CSRC, "gpd_write_scan.h"),
            os.path.join(ROOT, "include", "gpd_flow_expire.h"), os.path.join(CSRC, "gpd_flow_slots.h"),
-           os.path.join(ROOT, "include", "gpd_dns.h"), os.path.join(CSRC, "gpd_dns_walk.h")]
+           os.path.join(ROOT, "include", "gpd_dns.h"), os.path.join(CSRC, "gpd_dns_walk.h"),
+           os.path.join(CSRC, "gpd_locate.h"),
+           os.path.join(ROOT, "include", "gpd_tls.h"), os.path.join(CSRC, "gpd_tls_walk.h")]
 
 
 def _stale(target, deps):

@@ -11,7 +11,8 @@
 //   dns_scan_kernel     one workgroup: exclusive scan of the block counts
 //   dns_index_kernel    the candidates' packet indices in order
 //   dns_locate_kernel   one lane per candidate: the generic decoder over the packet again for the
-//                       last decoded layer's Payload — where the message lies (data_off, data_len)
+//                       last decoded layer's Payload — where the message lies (data_off, data_len;
+//                       gpd_locate.h, shared with gpd_tls.hip)
 //   dns_size_kernel     one lane per candidate: the full validating walk with the counting sink;
 //                       the message's entry count and name bytes, and the deferred total
 //   dns_sum_kernel      per 2048 candidates the sums of both counts (gpd_stream_util.h scan_sum)
@@ -29,6 +30,7 @@
 #include "gpd_compact.h"
 #include "gpd_dev_generic.h"
 #include "gpd_dns_walk.h"
+#include "gpd_locate.h"
 #include "gpd_stream_util.h"
 #include "../../include/gpd_dns.h"
 
@@ -79,47 +81,9 @@ __global__ __launch_bounds__(64) void dns_index_kernel(DnsArgs A) {
   compact_index(A.blk, A.mask, A.idx, (uint32_t)A.P.n);
 }
 
-// The last decoded layer's object: codes 1..4 are objects 0..3, the four IPv6 extension codes
-// share object 4, codes 9..15 are objects 5..11 (gpd.h).
-__device__ __forceinline__ uint32_t obj_of_code(uint32_t code) {
-  return code <= 4u ? code - 1u : code <= 8u ? (uint32_t)GPD_OBJ_IPV6_EXT : code - 4u;
-}
-
 template <bool PAGES>
 __global__ __launch_bounds__(256) void dns_locate_kernel(DnsArgs A) {
-  const KParams &P = A.P;
-  const uint32_t cnt = A.blk[A.nblk];
-  if (cnt <= blockIdx.x * 256u) return;
-  for (uint32_t k = threadIdx.x; k < P.image_words; k += 256) reinterpret_cast<uint32_t *>(g_lds)[k] = P.image[k];
-  __syncthreads();
-  const Tab<PAGES> T = make_tab<PAGES>(P);
-  const uint32_t dlen = (uint32_t)P.data_len;
-  const uint32_t options = (P.options & ~kDiagMask) | GPD_OPT_NO_CHECKSUMS | GPD_OPT_NO_FLOW_HASH;
-  for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < cnt; j += gridDim.x * 256u) {
-    const uint32_t i = A.idx[j];
-    const uint32_t off = min(P.offset[i], dlen), len = min(P.caplen[i], dlen - off);
-    gpd_ext_rec e;
-    decode_packet<true>(GlbSrc{P.data, off}, len, T, P.first, options, &e);
-    // decoded's last element: the highest nonzero nibble of the 32 codes
-    const uint64_t w = e.layer_codes[1] ? e.layer_codes[1] : e.layer_codes[0];
-    const uint32_t code = w ? (uint32_t)(w >> ((63u - (uint32_t)__builtin_clzll(w)) & ~3u)) & 15u : 0u;
-    const uint32_t obj = code ? obj_of_code(code) : (uint32_t)GPD_NOBJ;
-    uint32_t p_off = 0, p_len = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < (uint32_t)GPD_NOBJ; ++k)
-      if (k == obj) {
-        p_off = e.obj[k].payload_off;
-        p_len = e.obj[k].payload_len;
-      }
-    if (p_off > len) p_off = len;  // (never: a Payload lies inside the packet)
-    if (p_len > len - p_off) p_len = len - p_off;
-    const uint32_t st = P.rec ? P.rec[i].status : P.status[i];
-    const bool tp = code == GPD_C_TCP || code == GPD_C_UDP;
-    const bool sat = GPD_STATUS_SATURATED(st) || (tp && GPD_HDR_TP(P.hdr_off[i]) == GPD_HDR_NONE);
-    A.d_off[j] = p_off;
-    A.d_len[j] = p_len;
-    A.forced[j] = sat ? 1u : 0u;
-  }
+  locate_payloads<PAGES>(A.P, A.blk[A.nblk], A.idx, A.d_off, A.d_len, A.forced);  // gpd_locate.h
 }
 
 __global__ __launch_bounds__(256) void dns_size_kernel(DnsArgs A) {
