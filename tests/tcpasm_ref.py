@@ -138,19 +138,24 @@ class Model:
     def open_keys(self):
         return sorted(k for k in self.keys if self.conn(k) is not None)
 
+    def info(self, key):
+        """The key's (next_seq, flags, pages, page_bytes, last_seen_ns); all zero when it is closed."""
+        c = self.conn(key)
+        if c is None:
+            return (0, 0, 0, 0, 0)
+        noseq = c.nextSeq == TA.INVALID_SEQUENCE
+        nbytes, p = 0, c.first
+        while p is not None:
+            nbytes += len(p.r.Bytes)
+            p = p.next
+        return (0 if noseq else c.nextSeq, CONN_OPEN | (CONN_NOSEQ if noseq else 0), c.pages, nbytes,
+                int(max(c.lastSeen, 0)))
+
     def conns(self):
         out = np.zeros(self.id_bound, CONN_INFO_DTYPE)
         for k in self.keys:
-            c = self.conn(k)
-            if c is None:
-                continue
-            noseq = c.nextSeq == TA.INVALID_SEQUENCE
-            nbytes, p = 0, c.first
-            while p is not None:
-                nbytes += len(p.r.Bytes)
-                p = p.next
-            out[k] = (0 if noseq else c.nextSeq, CONN_OPEN | (CONN_NOSEQ if noseq else 0), c.pages, nbytes,
-                      int(max(c.lastSeen, 0)))
+            if self.conn(k) is not None:
+                out[k] = self.info(k)
         return out
 
     def stats(self, conns=None):
@@ -159,33 +164,25 @@ class Model:
                 "connections_with_pages": int((c["pages"] > 0).sum()), "pages": int(c["pages"].sum()),
                 "page_bytes": int(c["page_bytes"].sum())}
 
-    def run(self, segs=None, groups=None, packet=None, ts=None, now=0, T=0, close_all=False, flush_all=False):
-        """One gpd_tcp_assembler_run.  ts: None or a sequence of per-packet timestamps (ns)."""
+    def drive(self, work, packet=None, ts=None, now=0, T=0, close_all=False, flush_all=False):
+        """One run over `work`, a list of (key, the key's segment records in order): the keys
+        need only be hashable and sortable.  Returns (record rows, their Seen, stream rows with
+        the key first, byte chunks, bytes, calls)."""
         self.run_no += 1
-        grouped = []
-        if groups is not None:
-            for g in groups:
-                key = int(g["flow_id"])
-                if key == UNGROUPED:
-                    continue
-                assert key < self.id_bound
-                ev = self._asm(key)
-                grouped.append(key)
+        grouped = [k for k, _ in work]
+        for k in grouped:
+            self._asm(k)
         todo = grouped + [k for k in sorted(self.keys) if k not in set(grouped) and self.conn(k) is not None]
         for k in todo:
             ev = self.keys[k]
             ev.run_calls, ev.run_completed = [], 0
             ev.asm.run_no = self.run_no
-        if groups is not None:
-            for g in groups:
-                key = int(g["flow_id"])
-                if key == UNGROUPED:
-                    continue
-                a = self.keys[key].asm
-                for r in segs[int(g["start"]):int(g["start"]) + int(g["count"])]:
-                    a.cur_pkt = int(r["packet"])
-                    t = now if ts is None else int(ts[int(r["packet"])])
-                    a.AssembleSegment(key, r, packet(int(r["packet"])), ts=t)
+        for key, rs in work:
+            a = self.keys[key].asm
+            for r in rs:
+                a.cur_pkt = int(r["packet"])
+                t = now if ts is None else int(ts[int(r["packet"])])
+                a.AssembleSegment(key, r, packet(int(r["packet"])), ts=t)
         recs, seens, streams, chunks = [], [], [], []
         nbytes = ncalls = 0
         for k in todo:
@@ -213,6 +210,19 @@ class Model:
                 op, nseq, pages = CONN_OPEN | (CONN_NOSEQ if noseq else 0), 0 if noseq else int(c.nextSeq), c.pages
             streams.append((k, first_rec, len(recs) - first_rec, len(ev.run_calls), byte_off, nbytes - byte_off,
                             ev.run_completed, op, nseq, pages))
+        return recs, seens, streams, chunks, nbytes, ncalls
+
+    def run(self, segs=None, groups=None, packet=None, ts=None, now=0, T=0, close_all=False, flush_all=False):
+        """One gpd_tcp_assembler_run.  ts: None or a sequence of per-packet timestamps (ns)."""
+        work = []
+        if groups is not None:
+            for g in groups:
+                key = int(g["flow_id"])
+                if key == UNGROUPED:
+                    continue
+                assert key < self.id_bound
+                work.append((key, segs[int(g["start"]):int(g["start"]) + int(g["count"])]))
+        recs, seens, streams, chunks, nbytes, ncalls = self.drive(work, packet, ts, now, T, close_all, flush_all)
         conns = self.conns()
         st = self.stats(conns)
         out = (len(recs), len(streams), nbytes, ncalls, st["connections"], st["pages"], st["page_bytes"], 0)

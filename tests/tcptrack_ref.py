@@ -116,15 +116,16 @@ class Model:
     untracked), its TCP flag byte and its flow id (the connection's id is the flow id of the
     packet that created it, as the tracker's c is the record of the direction seen first)."""
 
-    def __init__(self, support_missing_establishment=False):
+    def __init__(self, support_missing_establishment=False, reverse=reverse_key):
         self.sme = bool(support_missing_establishment)
         self.conns = {}
+        self.reverse = reverse  # key.Reverse() for the keys the caller uses
 
     def getHalf(self, k):  # memory.go:169-180
         conn = self.conns.get(k)
         if conn is not None:
             return conn, TCPDirClientToServer
-        conn = self.conns.get(reverse_key(k))
+        conn = self.conns.get(self.reverse(k))
         if conn is not None:
             return conn, TCPDirServerToClient
         return None, None
@@ -169,6 +170,15 @@ class Model:
         for c in self.conns.values():
             if c.cid in ids:
                 c.fsm = TCPSimpleFSM(self.sme)
+
+    def drop(self, keys, live=()):
+        """StreamPool.remove of idle connections (memory.go:123-130): `keys` are the directional
+        keys whose records left the pool, `live` the keys still in it.  A connection leaves once
+        both of its records have: its own key is in `keys` and its reverse is not in `live`.  The
+        tuple's next packet, from either side, then makes a new connection."""
+        keys = set(keys)
+        for k in [k for k in self.conns if k in keys and self.reverse(k) not in live]:
+            del self.conns[k]
 
     def reset(self):
         for c in self.conns.values():
