@@ -19,7 +19,8 @@ without a table reset; its model is tests/flow_expire_ref.py) and the DNS messag
 layers.DNS for the packets whose decode stopped at LayerTypeDNS, validated and decompressed on the
 device; its model is tests/dns_ref.py) and the TLS record decode (tls.py: layers.TLS for the
 packets whose decode stopped at LayerTypeTLS and for reassembled streams where they lie; its model
-is tests/tls_ref.py).  (The stream
+is tests/tls_ref.py) and the DHCP message decode (dhcp.py: layers.DHCPv4 and layers.DHCPv6 for the
+packets whose decode stopped at LayerTypeDHCPv4 or LayerTypeDHCPv6; its model is tests/dhcp_ref.py).  (The stream
 assembler's restatement tests/tcpassembly_ref.py is the oracle of tcpstream.py.)
 """
 from . import layers
@@ -32,15 +33,15 @@ from .results import (BatchResult, Endpoint, FastHashes, Flow, FlowFromEndpoints
 __all__ = ["layers", "PacketBatch", "BatchResult", "DecodeError", "UnsupportedLayerType",
            "Endpoint", "Flow", "NewEndpoint", "NewFlow", "FlowFromEndpoints", "FastHashes",
            "MaxEndpointSize", "parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm", "tcpasm",
-           "tcptrack", "flowexpire", "dns", "tls"]
+           "tcptrack", "flowexpire", "dns", "tls", "dhcp"]
 
 
 def __getattr__(name):
     # the parser pulls in libgpd.so; import it lazily so that pure-host helpers
     # (pcap, synth, layers) work in environments that only build.
-    # (pcapng, pcapwrite, bpf, tcpassembly, tcpstream, ip4reasm, tcpasm, tcptrack, flowexpire, dns and tls bind their entry points onto libgpd.so too)
+    # (pcapng, pcapwrite, bpf, tcpassembly, tcpstream, ip4reasm, tcpasm, tcptrack, flowexpire, dns, tls and dhcp bind their entry points onto libgpd.so too)
     if name in ("parser", "pcapng", "pcapwrite", "bpf", "tcpassembly", "tcpstream", "ip4reasm", "tcpasm",
-                "tcptrack", "flowexpire", "dns", "tls"):
+                "tcptrack", "flowexpire", "dns", "tls", "dhcp"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("NgWriter", "NewNgWriter", "NewNgWriterInterface"):  # the pcapng writer (pcapwrite.py)

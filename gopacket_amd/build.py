@@ -39,7 +39,8 @@ SOURCES = [*KERNEL_SOURCES, os.path.join(CSRC, "gpd_runtime.cpp"),
            os.path.join(CSRC, "gpd_tcpseg.hip"), os.path.join(CSRC, "gpd_pcapngwrite.hip"),
            os.path.join(CSRC, "gpd_tcpstream.hip"), os.path.join(CSRC, "gpd_ip4reasm.hip"),
            os.path.join(CSRC, "gpd_tcpasm.hip"), os.path.join(CSRC, "gpd_tcptrack.hip"),
-           os.path.join(CSRC, "gpd_dns.hip"), os.path.join(CSRC, "gpd_tls.hip")]
+           os.path.join(CSRC, "gpd_dns.hip"), os.path.join(CSRC, "gpd_tls.hip"),
+           os.path.join(CSRC, "gpd_dhcp.hip")]
 HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h"),
            os.path.join(CSRC, "gpd_segwalk.h"), os.path.join(CSRC, "gpd_launch.h"),
            os.path.join(CSRC, "gpd_compact.h"),
@@ -63,7 +64,8 @@ HEADERS = [os.path.join(CSRC, "gpd_internal.h"), os.path.join(CSRC, "gpd_ctx.h")
            os.path.join(ROOT, "include", "gpd_flow_expire.h"), os.path.join(CSRC, "gpd_flow_slots.h"),
            os.path.join(ROOT, "include", "gpd_dns.h"), os.path.join(CSRC, "gpd_dns_walk.h"),
            os.path.join(CSRC, "gpd_locate.h"),
-           os.path.join(ROOT, "include", "gpd_tls.h"), os.path.join(CSRC, "gpd_tls_walk.h")]
+           os.path.join(ROOT, "include", "gpd_tls.h"), os.path.join(CSRC, "gpd_tls_walk.h"),
+           os.path.join(ROOT, "include", "gpd_dhcp.h"), os.path.join(CSRC, "gpd_dhcp_walk.h")]
 
 
 def _stale(target, deps):

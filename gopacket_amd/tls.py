@@ -295,7 +295,9 @@ class TLSResult:
         return m, r
 
     def message_bytes(self, msgs=None):
-        """`data` of every message, gathered on the device and copied once: a list of bytes."""
+        """`data` of every message, gathered on the device and copied once: a list of bytes.
+        dhcp.py's DHCPResult uses this function as its own: it may read `_source` (as the "batch"
+        form) and `to_host()[0]` (`packet`, `data_off`, `data_len`) of `self`, and nothing else."""
         from .parser import _torch
         torch = _torch()
         if msgs is None:
